@@ -2,8 +2,16 @@
 """Headline benchmark: FCOS ResNet-50-FPN training images/sec (whole node), 512x512, bs=16/GPU
 (BASELINE.json metric; configs[1] at N=1, configs[2] data-parallel at N>1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, ONE timed
+run of exactly K steps, the result line.  `--full` adds everything else the line can carry: the
+median of 3 timed runs (`--runs`), the in-step tower probe and the `roofline` blocks (runs of
+their own after the timed steps), the `dist.grad_allreduce` plan / traced step and the
+`cpu_baseline` leg.  `--dump-outputs DIR` writes what the last timed step handed its caller
+(per-image losses, head outputs, updated parameters) as float32 DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared array by array.
 
 `--gpus N` (N > 1) without a torchrun environment (no WORLD_SIZE) starts the N ranks itself: it
 runs `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1` on this same
@@ -217,9 +225,10 @@ def tower_alg_bytes(B, net, H, W):
 
 
 def timed_runs(step, load, pool, args, dev):
-    """W untimed warm-up steps, then `runs` timed runs of EXACTLY K steps each, every run bracketed
-    by a barrier + device synchronize on both sides and maxed over ranks (100 timed
-    steps, median of 3 runs).  Returns the per-run seconds; the reported line uses the median run."""
+    """W untimed warm-up steps, then `runs` timed runs of EXACTLY K steps each (one run; three with
+    --full), every run bracketed by a barrier + device synchronize on both sides and maxed over
+    ranks (100 timed steps, median of 3 runs).  Returns the per-run seconds; the
+    reported line uses the median run."""
     for i in range(args.warmup):
         load(pool[i % len(pool)])
         step()
@@ -241,6 +250,31 @@ def timed_runs(step, load, pool, args, dev):
 
 def _median_run(times):
     return sorted(times)[len(times) // 2]
+
+
+DUMP_ELEMS = 4 << 20           # per dumped array: 16 MB of float32, four arrays stay under 64 MB
+
+
+def dump_outputs(path, tr, net, head_cols=None):
+    """--dump-outputs: what the last timed step handed its caller, each as float32 <path>/<name>.npy --
+    the per-image losses (`step()`'s return value), the heads' outputs (`tr.outputs`, the columns the
+    heads store: head_cols = (reg, cls)) and the updated parameters.  An array of more than DUMP_ELEMS
+    elements is written as a fixed sample of its flattened elements (seeded: the same sorted indices
+    in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"losses": tr.losses, "params": net.store.flat}
+    if head_cols is not None:
+        reg, cls = tr.outputs
+        arrays["head_reg"], arrays["head_cls"] = reg[..., :head_cols[0]], cls[..., :head_cols[1]]
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(2024)
+            idx = torch.randint(t.numel(), (DUMP_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _cores():
@@ -514,7 +548,8 @@ def _line(metric, world, B, args, times, extra):
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000.0 * el / args.steps, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
            "runs": {"n": len(times), "img_s": [round(world * B * args.steps / t, 3) for t in times],
-                    "reported": "median run (SURVEY.md 8d: median of 3 runs of the timed steps)"}}
+                    "reported": "median run (SURVEY.md 8d: median of 3 runs of the timed steps)" if len(times) > 1
+                                else "the one timed run (--full: median of 3)"}}
     if torch.cuda.is_available():     # peak HBM the step's tensors held (allocator high-water mark)
         out["peak_hbm_gib"] = round(torch.cuda.max_memory_allocated() / 2.0 ** 30, 3)
     out.update(extra)
@@ -533,28 +568,34 @@ def bench_retinanet(args):
     S = args.size if args.size != 512 else 640
     rn = RetinaNet(80, {}, anchor_sizes=[20.0, 40.0, 80.0, 160.0, 320.0])
     net = rn.model
-    net.tower_probe = torch.zeros(4, dtype=torch.int64, device=dev)
+    net.tower_probe = torch.zeros(4, dtype=torch.int64, device=dev) if args.full else None
     tr = RetinaTrainer(net, rn, B, S, n_max=50, world=world, use_graph=not args.no_graph)
     pool = [synthetic_coco_batch(3 * B, S, 80, n_max=50, seed=4321 + 97 * rank + i, device=dev) for i in range(2)]
     for i in range(2):                           # capture + one replay before the probe counts
         tr.load_candidates(*pool[i % 2])
         tr.step()
     torch.cuda.synchronize()
-    net.tower_probe.zero_()
+    if net.tower_probe is not None:
+        net.tower_probe.zero_()
     times = timed_runs(tr.step, lambda b: tr.load_candidates(*b), pool, args, dev)
     if rank != 0:
         dist.barrier()
         return
-    in_s, in_n = nn.probe_seconds(net.tower_probe)
-    net.tower_probe = None
-    out = _line("training images/sec (whole node), RetinaNet-R50-FPN COCO 640x640 bs=8/GPU", world, B, args, times, {
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr, net, head_cols=(36, 9 * 80))
+    extra = {
         "data": "synthetic COCO-shaped: 3*bs candidates/step, 1+Poisson(6.3) boxes, C=80; random init",
         "config": {"workload": "RetinaNet R50-FPN train step (assign 3bs candidates + select + fwd + loss + "
                                "bwd + clip/SGD)", "model": "RetinaNet-ResNet50-FPN", "global_batch": B * world,
                    "image_size": S, "parallelism": "dp%d" % world},
-        "roofline": tower_roofline(net, B, S, S, in_s, in_n, pmc=False),
-        "last_step_losses_cls_reg": [round(x, 3) for x in tr.losses.double().sum(0).cpu().tolist()]})
-    if world == 1 and not args.no_cpu_baseline:
+        "last_step_losses_cls_reg": [round(x, 3) for x in tr.losses.double().sum(0).cpu().tolist()]}
+    if args.full:
+        in_s, in_n = nn.probe_seconds(net.tower_probe)
+        net.tower_probe = None
+        extra["roofline"] = tower_roofline(net, B, S, S, in_s, in_n, pmc=False)
+    out = _line("training images/sec (whole node), RetinaNet-R50-FPN COCO 640x640 bs=8/GPU", world, B, args, times,
+                extra)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_retina(S, 80)
     print(json.dumps(out), flush=True)
     if world > 1:
@@ -579,14 +620,19 @@ def bench_centernet(args):
     if rank != 0:
         dist.barrier()
         return
-    out = _line("training images/sec (whole node), CenterNet-hourglass VOC 512x512 bs=8/GPU", world, B, args, times, {
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr, net)
+    extra = {
         "data": "synthetic VOC-shaped: U[-1,1) images, 1+Poisson(1.4) boxes, C=20; random init",
         "config": {"workload": "CenterNet hourglass train step (centroid targets + fwd + loss + bwd + clip/Adam), "
                                "BN sub-batch 2", "model": "CenterNet-separable-hourglass-nf128",
                    "global_batch": B * world, "image_size": S, "parallelism": "dp%d" % world},
-        "roofline": centernet_roofline(net, tr, B, S),
-        "last_step_losses_cls_reg": [round(x, 3) for x in tr.losses.double().sum(0).cpu().tolist()]})
-    if world == 1 and not args.no_cpu_baseline:
+        "last_step_losses_cls_reg": [round(x, 3) for x in tr.losses.double().sum(0).cpu().tolist()]}
+    if args.full:
+        extra["roofline"] = centernet_roofline(net, tr, B, S)
+    out = _line("training images/sec (whole node), CenterNet-hourglass VOC 512x512 bs=8/GPU", world, B, args, times,
+                extra)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_centernet(S, NUM_CLASSES)
     print(json.dumps(out), flush=True)
     if world > 1:
@@ -660,7 +706,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--runs", type=int, default=3, help="timed runs of --steps steps each; the line reports the median")
+    ap.add_argument("--runs", type=int, default=None,
+                    help="timed runs of --steps steps each; the line reports the median (default 1; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: median of 3 timed runs, in-step tower probe, "
+                         "roofline blocks, gradient all-reduce plan / trace, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses, head outputs, updated parameters) as "
+                         "float32 DIR/<name>.npy")
     ap.add_argument("--bs", type=int, default=16)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--no-graph", action="store_true")
@@ -672,6 +725,8 @@ def main():
                          "(R50-FPN 640x640 COCO-80 bs=8/GPU), a side line")
     ap.add_argument("--dry-run", action="store_true", help="form the rank group, print the world, no GPU work")
     args = ap.parse_args()
+    if args.runs is None:
+        args.runs = 3 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if args.dry_run:
@@ -688,8 +743,8 @@ def main():
     B, H, W = args.bs, args.size, args.size
     net = FCOSNet(NUM_CLASSES, device=dev, seed=0)       # identical init on every rank
     # in-step timing of the dominant kernel: each paired tower forward launch times itself from inside
-    # (cvl_probe_arm: the slot rides in the launch arguments captured into the step graph)
-    net.tower_probe = None if args.no_probe else torch.zeros(4, dtype=torch.int64, device=dev)
+    # (cvl_probe_arm: the slot rides in the launch arguments captured into the step graph); --full only
+    net.tower_probe = torch.zeros(4, dtype=torch.int64, device=dev) if args.full and not args.no_probe else None
     tr = FCOSTrainer(net, B, (H, W), world=world, use_graph=not args.no_graph)
     pool = [synthetic_batch(B, H, W, NUM_CLASSES, seed=1234 + 97 * rank + i, device=dev) for i in range(4)]
     for i in range(2):                           # capture + one replay before the probe counts
@@ -699,30 +754,36 @@ def main():
     if net.tower_probe is not None:
         net.tower_probe.zero_()                  # count only the timed steps' tower launches
     times = timed_runs(tr.step, lambda b: tr.load_batch(*b), pool, args, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, net, head_cols=(5, NUM_CLASSES))
     losses = tr.losses.detach().double().sum(0).cpu().tolist()
     img_s = world * B * args.steps / _median_run(times)
     fl_img = train_flops_per_image(H, W)
-    in_s, in_n = nn.probe_seconds(net.tower_probe) if net.tower_probe is not None else (None, 0)
-    grad_ar = dp_timeline(tr, pool[0])                  # (replays the graph: the probe buffer stays live)
+    if args.full:
+        in_s, in_n = nn.probe_seconds(net.tower_probe) if net.tower_probe is not None else (None, 0)
+        grad_ar = dp_timeline(tr, pool[0])              # (replays the graph: the probe buffer stays live)
     if rank != 0:
         dist.barrier()
         return
-    net.tower_probe = None
-    roof = tower_roofline(net, B, H, W, in_s, in_n, pmc=(B, H, W) == (16, 512, 512))
-    roof["backbone_3x3"] = measure_backbone_3x3(net, B, H, W)
-    out = _line(METRIC, world, B, args, times, {
+    extra = {
         "data": "synthetic VOC-shaped: U[-1,1) 512x512 images, 1+Poisson(1.4) boxes, log-uniform 12-480 px, "
                 "C=20; random-init (Keras glorot) weights",
         "config": {"workload": "FCOS ResNet-50-FPN train step (targets + fwd + loss + bwd + clip/SGD), "
                                "512x512, bs=16 per GPU",
                    "model": "FCOS-ResNet50-FPN", "global_batch": B * world, "image_size": H,
                    "parallelism": "dp%d" % world},
-        "roofline": roof,
-        "dist": dict(dist_info(world), grad_allreduce=grad_ar),
+        "dist": dist_info(world),
         "model_flops_per_image": fl_img,
         "step_mfma_frac": round(img_s / world * fl_img / 1e12 / PEAK_BF16_TFLOPS, 4),
-        "last_step_losses_cls_reg_cen": [round(x, 3) for x in losses]})
-    if world == 1 and not args.no_cpu_baseline:
+        "last_step_losses_cls_reg_cen": [round(x, 3) for x in losses]}
+    if args.full:
+        net.tower_probe = None
+        roof = tower_roofline(net, B, H, W, in_s, in_n, pmc=(B, H, W) == (16, 512, 512))
+        roof["backbone_3x3"] = measure_backbone_3x3(net, B, H, W)
+        extra["roofline"] = roof
+        extra["dist"] = dict(dist_info(world), grad_allreduce=grad_ar)
+    out = _line(METRIC, world, B, args, times, extra)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(H, W)
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -3,20 +3,22 @@
 # step with the all-reduce path live on a one-rank RCCL group (CVL_DISPATCH=dp_force_sync: the
 # fwd+bwd graph captured in hook-split segments, async all-reduces between segment replays, the
 # update queued behind them).  Same box, alternating, 2 rounds; the force-sync lines carry the
-# per-group enqueue points (dist.grad_allreduce); a third arm keeps the segmented graphs but issues
-# no collective (CVL_DISPATCH=dp_segments_only).  Output: gpurun_out/dp_*.json
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
+# per-group enqueue points (dist.grad_allreduce, bench.py --full); a third arm keeps the segmented
+# graphs but issues no collective (CVL_DISPATCH=dp_segments_only).  Output: $OUT/dp_*.json (default out/)
+cd "$(dirname "$0")/.." || exit 1
+OUT=${OUT:-out}
+mkdir -p "$OUT"
+export TMPDIR=${TMPDIR:-/tmp}
 for r in 1 2; do
-  timeout -k 10 150 python -u bench.py --steps 30 --runs 3 --no-cpu-baseline > gpurun_out/dp_off_$r.json 2> gpurun_out/dp_off_$r.err || exit 1
+  timeout -k 10 150 python -u bench.py --steps 30 --runs 3 > "$OUT"/dp_off_$r.json 2> "$OUT"/dp_off_$r.err || exit 1
   MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29600 + r)) RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 CVL_DISPATCH=dp_force_sync \
-    timeout -k 10 150 python -u bench.py --steps 30 --runs 3 --no-cpu-baseline > gpurun_out/dp_on_$r.json 2> gpurun_out/dp_on_$r.err || exit 1
+    timeout -k 10 150 python -u bench.py --full --no-probe --steps 30 --runs 3 --no-cpu-baseline > "$OUT"/dp_on_$r.json 2> "$OUT"/dp_on_$r.err || exit 1
   MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29610 + r)) RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 CVL_DISPATCH=dp_force_sync,dp_segments_only \
-    timeout -k 10 150 python -u bench.py --steps 30 --runs 3 --no-cpu-baseline > gpurun_out/dp_seg_$r.json 2> gpurun_out/dp_seg_$r.err || exit 1
-  python3 - "$r" <<'EOF'
+    timeout -k 10 150 python -u bench.py --steps 30 --runs 3 > "$OUT"/dp_seg_$r.json 2> "$OUT"/dp_seg_$r.err || exit 1
+  python3 - "$r" "$OUT" <<'EOF'
 import json, sys
-r = sys.argv[1]
-off, on, seg = (json.loads(open("gpurun_out/dp_%s_%s.json" % (k, r)).read().strip().splitlines()[-1])
+r, out = sys.argv[1:3]
+off, on, seg = (json.loads(open("%s/dp_%s_%s.json" % (out, k, r)).read().strip().splitlines()[-1])
                 for k in ("off", "on", "seg"))
 print("round %s: default %.1f img/s (%.3f ms)  force-sync %.1f img/s (%.3f ms)  overhead %.2f %%  "
       "(segmented graphs alone, no collective: %.3f ms, %.2f %%)"
