@@ -12,6 +12,8 @@ constexpr int kMaxSeg = CVL_CONV_MAX_SEG;
 
 // kernel variant of the last cvl_conv_igemm call on this host thread (cvl_conv_igemm_last_kernel)
 extern thread_local int g_cvl_conv_last_kernel;
+// K-tile depth (32 / 64) of the last X or P launch on this host thread (cvl_conv_igemm_last_ktile)
+extern thread_local int g_cvl_conv_last_ktile;
 
 // Workgroups are dispatched round-robin over the 8 XCDs (hardware id b runs on XCD b % 8).  This
 // bijective remap gives consecutive LOGICAL ids to the workgroups of one XCD, so tiles that read

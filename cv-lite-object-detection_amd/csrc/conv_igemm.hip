@@ -579,10 +579,12 @@ __global__ void zero_gaps_kernel(void* dst, int is_f32, long dst_base, long dst_
 }
 
 thread_local int g_cvl_conv_last_kernel = CVL_CK_NONE;
+thread_local int g_cvl_conv_last_ktile = 0;
 thread_local const void* g_cvl_ymask = nullptr;
 thread_local int g_cvl_ymask_used = 0;
 
 extern "C" int cvl_conv_igemm_last_kernel(void) { return g_cvl_conv_last_kernel; }
+extern "C" int cvl_conv_igemm_last_ktile(void) { return g_cvl_conv_last_ktile; }
 
 extern "C" const char* cvl_conv_kernel_name(int code) {
   switch (code) {
@@ -677,6 +679,7 @@ int conv_igemm_call(const cvl_conv_desc* d, const void* src, void* dst, uint64_t
   acc_u64* bn_stats = reinterpret_cast<acc_u64*>(bn_stats_acc);
   hipStream_t s = (hipStream_t)stream;
   g_cvl_conv_last_kernel = CVL_CK_NONE;
+  g_cvl_conv_last_ktile = 0;
   CVL_CHECK_ARG(d);
   if (d->prec == CVL_PREC_F32) return cvl_conv_f32(d, src, dst, bn_stats, s);    // parity mode
   CVL_CHECK_ARG(d->prec == CVL_PREC_BF16);

@@ -8,14 +8,15 @@
 // workgroup kernels pay, per 256-row tile, the set-up, the DMA prologue and the epilogue (store +
 // statistics) back to back: 3-5 us per tile against ~0.5 us of MFMA work.  Here:
 // * One workgroup per CU loops over its tiles (one N tile, a contiguous chunk of M tiles), and the
-//   LDS-DMA stream of 32-deep K-tiles runs ACROSS tiles: while tile t's last K-tile is
-//   multiplied and its epilogue stores, the first K-tiles of tile t + G are already in flight.
+//   LDS-DMA stream of K-tiles (64 deep where K % 64 == 0, else 32) runs ACROSS tiles: while tile
+//   t's last K-tile is multiplied and its epilogue stores, the first K-tiles of tile t + G are
+//   already in flight.
 // * Ring of NS slots, D = NS - 1 K-tiles issued ahead; per K-tile one counted vmcnt wait (this
 //   wave's pieces) + one barrier (everyone's, which also certifies that every wave is done reading
 //   the previous K-tile, whose slot the issue that follows refills).
-//   Every wave issues the same number of pieces per K-tile (BN = 64: waves 4-7 issue an
-//   out-of-range piece into a dummy area), and K-tiles past the end issue out-of-range pieces, so
-//   one static count fits every wait; epilogue stores only make the waits more conservative
+//   Every wave issues the same number of pieces per K-tile (32-deep K-tiles at BN = 64: waves 4-7
+//   issue an out-of-range piece into a dummy area), and K-tiles past the end issue out-of-range
+//   pieces, so one static count fits every wait; epilogue stores only make the waits more conservative
 //   (vmcnt completes in issue order).
 // * Swapped MFMA operands: D = W_tile . A_tile^T, so a lane's accumulator quad holds 4 CONSECUTIVE
 //   output channels of one pixel: the epilogue stores 8 bytes (4 bf16) per lane straight from the
@@ -25,33 +26,44 @@
 //   the 16 rows of a lane quad, the wave rows combined through LDS in a fixed order, one fp64
 //   atomic pair per image, channel and workgroup; a tile lies inside one image: host checks
 //   H*W % 256 == 0).
-// * Operand images: 64-B rows with the XOR swizzle (r >> 1) & 3 on the 16-B chunk, applied to the
-//   per-lane DMA source offset (conflict-free ds_read_b128 fragment reads), as conv_igemm_x.hip.
+// * Operand images: rows of BK bf16 with an XOR swizzle on the 16-B chunk, applied to the per-lane
+//   DMA source offset (conflict-free ds_read_b128 fragment reads), as conv_igemm_x.hip.
+//   64-deep K-tiles (every ResNet / FPN channel count): 128-B rows, 8 rows x 8 chunks per 1-KiB DMA
+//   instruction (lane l: row l >> 3, chunk (l & 7) ^ ((row >> 1) & 7)), so every piece of a row is a
+//   full 128-B line: ~17 cycles of the CU's address path per instruction against ~31 for the
+//   sixteen 64-B row pieces of a 32-deep K-tile (profiles/r07_k64_gate.md), and half the barriers
+//   per FLOP.  The two 32-deep halves of a K-tile are multiplied in k order, so the accumulation
+//   sequence -- and every output bit -- is that of the 32-deep form (CVL_DISPATCH=p_k64=0), which
+//   stays for K % 64 != 0 and the 256-wide tile (64-B rows, swizzle (r >> 1) & 3).
 #include "conv_common.h"
 
 namespace {
 
-constexpr int NT = 512, BM = 256, BK = 32;
+constexpr int NT = 512, BM = 256;
 constexpr unsigned kRecords = 0x7fffffffu;
 constexpr unsigned kOOB = 0x80000000u;
 constexpr int LDS_BYTES = 163840;
 
-__device__ __forceinline__ int swz4(int r) { return (r >> 1) & 3; }
+// chunk swizzle of row r of an image with BK-deep rows (BK / 8 chunks)
+template <int BK>
+__device__ __forceinline__ int swz(int r) { return (r >> 1) & (BK / 8 - 1); }
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, const void* lds_dst, unsigned voff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, (int)voff, 0,
                                            0, 0);
 }
 
-template <int BN>
+template <int BN, int BK>
 struct PCfg {
   static constexpr int WGM = BN == 256 ? 2 : 4, WGN = 8 / WGM;
   static constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 16, TN = WN / 16;
   static constexpr int SLOT_B = (BM + BN) * BK * 2;        // bytes per ring slot (A then B)
-  static constexpr int BPW = BN >= 128 ? BN / 128 : 1;     // B pieces per wave per K-tile
-  static constexpr int PW = 2 + BPW;                       // DMA pieces per wave per K-tile
+  static constexpr int PR = 8 * 64 * 16 / (BK * 2);        // rows per DMA piece of all 8 waves (128 / 64)
+  static constexpr int APW = BM / PR;                      // A pieces per wave per K-tile
+  static constexpr int BPW = BN >= PR ? BN / PR : 1;       // B pieces per wave per K-tile
+  static constexpr int PW = APW + BPW;                     // DMA pieces per wave per K-tile
   static constexpr int RED_B = WGM * BN * 2 * 4;           // statistics reduction area
-  static constexpr int DUMMY_B = BN == 64 ? 4 * 1024 : 0;  // sink of the BN = 64 filler pieces
+  static constexpr int DUMMY_B = BN < PR ? 4 * 1024 : 0;   // sink of the filler pieces (BN 64, 32-deep)
   static constexpr int NS = (LDS_BYTES - RED_B - DUMMY_B) / SLOT_B;
   static constexpr int D = NS - 1;                         // K-tiles in flight
   static_assert(D >= 2, "ring too short");
@@ -88,9 +100,9 @@ __device__ __forceinline__ s16x8 gload16_untracked(const void* p) {
 }
 __device__ __forceinline__ void pin16(s16x8& v) { asm volatile("" : "+v"(v)); }
 
-template <int BN, bool RELU, bool F32, int BS = 0, bool ACC = false>
+template <int BN, int BK, bool RELU, bool F32, int BS = 0, bool ACC = false>
 __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles) {
-  using C = PCfg<BN>;
+  using C = PCfg<BN, BK>;
   constexpr int TM = C::TM, TN = C::TN, NS = C::NS, D = C::D;
   __shared__ __attribute__((aligned(16))) char lds[C::NS * C::SLOT_B + C::RED_B + C::DUMMY_B];
   float* red = reinterpret_cast<float*>(lds + NS * C::SLOT_B);
@@ -116,23 +128,25 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
   const int Cin2 = a.Cin * 2;
   const int K2 = a.K * 2;
 
-  // DMA pieces of this lane: A rows p * 128 + wave * 16 + lane / 4 (p = 0, 1), B rows
-  // j * 128 + wave * 16 + lane / 4 (BN >= 128) or wave * 16 + lane / 4 on waves 0-3 (BN = 64);
-  // 16-B chunk lane % 4, swizzled
-  const int prow = wave * 16 + (lane >> 2), ch = lane & 3;
-  const unsigned chs = (unsigned)((ch ^ swz4(prow)) * 16);
+  // DMA pieces of this lane, 32-deep: A rows p * 128 + wave * 16 + lane / 4 (p = 0, 1), B rows
+  // j * 128 + wave * 16 + lane / 4 (BN >= 128) or wave * 16 + lane / 4 on waves 0-3 (BN = 64),
+  // 16-B chunk lane % 4, swizzled; 64-deep: A rows p * 64 + wave * 8 + lane / 8 (p = 0..3), B rows
+  // j * 64 + wave * 8 + lane / 8, chunk lane % 8, swizzled
+  constexpr int LPR = BK / 8, PR = C::PR, WR = PR / 8;    // lanes per row, rows per piece, per wave
+  const int prow = wave * WR + lane / LPR, ch = lane % LPR;
+  const unsigned chs = (unsigned)((ch ^ swz<BK>(prow)) * 16);
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a.src, (short)0, (int)kRecords, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)S.w, (short)0, (int)kRecords, 0x00020000);
 
   // issue cursor: K-tile ik of my tile it (global stream index ig, ring slot islot)
   int ik = 0, it = 0, islot = 0;
-  unsigned ia[2], ib[C::BPW];
+  unsigned ia[C::APW], ib[C::BPW];
   const int n0 = (L % ntn) * BN;
   auto set_issue_tile = [&](int k) {
     const int m0 = (mt0 + k) * BM;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int ml = ((a.dbg & 16) ? 0 : m0) + p * 128 + prow;
+    for (int p = 0; p < C::APW; ++p) {
+      const int ml = ((a.dbg & 16) ? 0 : m0) + p * PR + prow;
       long pix;
       if (dense_src) {
         pix = S.src_base + ml;
@@ -145,7 +159,7 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
     }
 #pragma unroll
     for (int j = 0; j < C::BPW; ++j) {
-      const int nr = n0 + (BN >= 128 ? j * 128 : 0) + prow;
+      const int nr = n0 + j * PR + prow;
       ib[j] = (unsigned)(nr * K2) + chs;
     }
   };
@@ -156,12 +170,12 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
     char* sb = sa + BM * BK * 2;
     const unsigned ko = (unsigned)(ik * BK * 2);
 #pragma unroll
-    for (int p = 0; p < 2; ++p) dma16(rsA, sa + (p * 128 + wave * 16) * BK * 2, live ? ia[p] + ko : kOOB);
-    if (BN >= 128) {
+    for (int p = 0; p < C::APW; ++p) dma16(rsA, sa + (p * PR + wave * WR) * BK * 2, live ? ia[p] + ko : kOOB);
+    if (BN >= PR) {
 #pragma unroll
-      for (int j = 0; j < C::BPW; ++j) dma16(rsB, sb + (j * 128 + wave * 16) * BK * 2, live ? ib[j] + ko : kOOB);
+      for (int j = 0; j < C::BPW; ++j) dma16(rsB, sb + (j * PR + wave * WR) * BK * 2, live ? ib[j] + ko : kOOB);
     } else if (wave < 4) {
-      dma16(rsB, sb + (wave * 16) * BK * 2, live ? ib[0] + ko : kOOB);
+      dma16(rsB, sb + (wave * WR) * BK * 2, live ? ib[0] + ko : kOOB);
     } else {
       dma16(rsB, dummy + (wave - 4) * 1024, kOOB);
     }
@@ -176,16 +190,17 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
   const int wm = wave / C::WGN, wn = wave % C::WGN;
   const int lr = lane & 15, lg = lane >> 4;
   // fragment byte offsets within a slot: A row wm*WM + i*16 + lr, B row wn*WN + j*16 + lr, k chunk lg
+  // (64-deep: of the K-tile's first half; the second half's chunk 4 + lg is at the offset ^ 64)
   unsigned fao[TM], fbo[TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int r = wm * C::WM + i * 16 + lr;
-    fao[i] = (unsigned)(r * BK * 2 + ((lg ^ swz4(r)) * 16));
+    fao[i] = (unsigned)(r * BK * 2 + ((lg ^ swz<BK>(r)) * 16));
   }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int r = wn * C::WN + j * 16 + lr;
-    fbo[j] = (unsigned)(BM * BK * 2 + r * BK * 2 + ((lg ^ swz4(r)) * 16));
+    fbo[j] = (unsigned)(BM * BK * 2 + r * BK * 2 + ((lg ^ swz<BK>(r)) * 16));
   }
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -450,7 +465,7 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
   int rslot = 0, ck = 0, ct = 0;
   for (int g = 0; g < total; ++g) {
     wait_vm<(D - 1) * C::PW>();                    // this wave's pieces of K-tile g landed
-    __builtin_amdgcn_s_barrier();                  // ... everyone's; slot of K-tile g - 2 free
+    __builtin_amdgcn_s_barrier();                  // ... everyone's; slot of K-tile g - 1 free
     asm volatile("" ::: "memory");
     issue();                                       // K-tile g + D
     if (ACC && ck == 0) {                          // old dst chunks of tile ct for the epilogue
@@ -496,17 +511,20 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
         }
     }
     const char* sl = lds + rslot * C::SLOT_B;
-    s16x8 fa[TM], fb[TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const s16x8*>(sl + fao[i]);
+    for (int kh = 0; kh < BK / 32; ++kh) {         // the 32-deep halves in k order
+      s16x8 fa[TM], fb[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const s16x8*>(sl + fbo[j]);
+      for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const s16x8*>(sl + (fao[i] ^ (unsigned)(kh * 64)));
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+      for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const s16x8*>(sl + (fbo[j] ^ (unsigned)(kh * 64)));
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[j]),
-                                                             __builtin_bit_cast(bf16x8, fa[i]), acc[i][j], 0, 0, 0);
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[j]),
+                                                               __builtin_bit_cast(bf16x8, fa[i]), acc[i][j], 0, 0, 0);
+    }
     rslot = rslot == NS - 1 ? 0 : rslot + 1;
     if (++ck == nk) {
       ck = 0;
@@ -523,7 +541,7 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
 // Runs a 1x1 launch on the persistent kernel; -1 when it does not apply.
 int cvl_conv_igemm_p(const cvl_conv_desc* d, const ConvArgs& a0, hipStream_t s) {
   if (cvl_dispatch_flag("no_p")) return -1;
-  if (d->KH != 1 || d->KW != 1 || d->pad_t || d->pad_l || a0.relu_in || a0.nseg != 1 || a0.K % BK) return -1;
+  if (d->KH != 1 || d->KW != 1 || d->pad_t || d->pad_l || a0.relu_in || a0.nseg != 1 || a0.K % 32) return -1;
   // bsum forms: z-mask without beta; y-mask (residual unit) with the beta accumulate
   // (the residual form also on the strided data gradient's scatter, dst_up 2: the gap pixels' dy is 0,
   // so the scattered rows' sums are the map's)
@@ -559,25 +577,32 @@ int cvl_conv_igemm_p(const cvl_conv_desc* d, const ConvArgs& a0, hipStream_t s) 
   if (grid < 1) return -1;
   ConvArgs a = a0;
   a.dbg = cvl_tune_int("CVL_P_ABLATE", 0);
+  // 64-deep K-tiles (128-B operand rows) wherever K allows; the 256-wide tile's ring has no room
+  const bool k64 = a.K % 64 == 0 && use != 256 && cvl_dispatch_int("p_k64", 1);
   g_cvl_conv_last_kernel = CVL_CK_P;
-#define CVL_P_LAUNCH(BN_, ACC_)                                                                                 \
+  g_cvl_conv_last_ktile = k64 ? 64 : 32;
+#define CVL_P_LAUNCH(BN_, BK_, ACC_)                                                                                 \
   do {                                                                                                      \
-    if (a.dst_f32) {                                                                                        \
-      if (a.relu_out) hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, true, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
-      else hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, false, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);            \
+    if (a.bsum && a.by) {                                                                                   \
+      hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 2, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
+    } else if (a.bsum) {                                                                                    \
+      hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 1>), dim3(grid), dim3(NT), 0, s, a, ntiles);         \
+    } else if (a.dst_f32) {                                                                                 \
+      if (a.relu_out) hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
+      else hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);            \
     } else if (a.relu_out) {                                                                                \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, true, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                 \
+      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                 \
     } else if (a.beta != 0.f && !cvl_tune_flag("CVL_P_NO_ACC")) {                                            \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, false, false, false, ACC_>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
+      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false, false, ACC_>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
     } else {                                                                                                \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, false, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                \
+      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                \
     }                                                                                                       \
   } while (0)
-  if (a.bsum && a.by) hipLaunchKernelGGL((conv_igemm_p_kernel<64, false, false, 2, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);
-  else if (a.bsum) hipLaunchKernelGGL((conv_igemm_p_kernel<64, false, false, 1>), dim3(grid), dim3(NT), 0, s, a, ntiles);
-  else if (use == 256) CVL_P_LAUNCH(256, false);      // (the 256-wide ACC form spills)
-  else if (use == 128) CVL_P_LAUNCH(128, true);
-  else CVL_P_LAUNCH(64, true);
+  if (use == 256) CVL_P_LAUNCH(256, 32, false);       // (the 256-wide ACC form spills)
+  else if (use == 128 && k64) CVL_P_LAUNCH(128, 64, true);
+  else if (use == 128) CVL_P_LAUNCH(128, 32, true);
+  else if (k64) CVL_P_LAUNCH(64, 64, true);
+  else CVL_P_LAUNCH(64, 32, true);
 #undef CVL_P_LAUNCH
   return cvl_launch_status();
 }

@@ -43,6 +43,9 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, const cvl_bf16* 
 // barrier apart (each SIMD alternates one wave's MFMA segment with the other's load segment), so a
 // K-tile is waited for one phase before it is read and a slot is refilled two phases after its
 // last read.  Operand images: 64-B rows, chunk swizzle (r >> 1) & 3 (conflict-free fragment reads).
+// 64-deep K-tiles (128-B rows, half the DMA instructions and address-path cycles) were built twice
+// on this tile and measured slower, alone and in the step (profiles/r07_k64_gate.md section 3):
+// the 32-deep K-tiles stay.
 // ---------------------------------------------------------------------------------------------
 constexpr int BK32 = 32;
 constexpr int SLOT = 2 * 256 * BK32;      // bf16 elements per ring slot (A + B, 32 KiB)
@@ -321,6 +324,7 @@ int cvl_conv_igemm_x(const cvl_conv_desc* d, const ConvArgs& a, hipStream_t s) {
   am.dbg = cvl_tune_int("CVL_X_ABLATE", 0);     // measurement builds (tools/x32_*.py): ablation bits
   am.probe = reinterpret_cast<unsigned long long*>(cvl_probe_current(true));   // bench.py's in-step timing
   g_cvl_conv_last_kernel = CVL_CK_X32;
+  g_cvl_conv_last_ktile = BK32;
   // SW epilogue: bf16 destination in 8-channel chunks, no BN statistics, no beta
   const bool sw = !a.dst_f32 && !a.stats && a.beta == 0.f && a.n_store % 8 == 0 && a.ld_dst % 8 == 0 &&
                   a.dst_coff % 8 == 0 && !cvl_dispatch_flag("x_no_sw");

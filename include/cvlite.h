@@ -198,6 +198,9 @@ enum { CVL_CK_NONE = 0, CVL_CK_BASE = 1, CVL_CK_BASE_SPLITK = 2, CVL_CK_L64 = 3,
        CVL_CK_WG_S = 8, CVL_CK_WG_L128 = 9, CVL_CK_WG_L256 = 10, CVL_CK_WG_X = 11, CVL_CK_X32H = 12, CVL_CK_WG_SN = 13,
        CVL_CK_H64 = 14, CVL_CK_WG_H = 15, CVL_CK_P = 16 };
 int cvl_conv_igemm_last_kernel(void);
+/* K-tile depth (32 or 64 bf16) of the last launch of the tower kernel (CVL_CK_X32) or the persistent
+ * 1x1 kernel (CVL_CK_P) on this host thread; 0 before the first one. */
+int cvl_conv_igemm_last_ktile(void);
 const char* cvl_conv_kernel_name(int code);
 
 /* Measurement hook (no reference counterpart: bench.py's in-step roofline timing).  cvl_probe_arm

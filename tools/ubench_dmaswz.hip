@@ -11,7 +11,8 @@ __device__ __forceinline__ void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
-// MODE 0 lane-linear, 1 XOR swizzle by row, 2 out of range (zeros), 3 swizzle by (row >> 1) & 3
+// MODE 0 lane-linear, 1 XOR swizzle by row, 2 out of range (zeros), 3 swizzle by (row >> 1) & 3,
+// 4 swizzle by (row >> 1) & 7 (the 128-B-row image of the 64-deep K-tiles: 8 rows x 8 chunks)
 template <int ROWB, int MODE>
 __global__ void __launch_bounds__(512) k_rows(const char* src, unsigned long fbytes, int pitch, int iters, int* sink) {
   __shared__ __attribute__((aligned(16))) char lds[128 * 1024];
@@ -22,6 +23,7 @@ __global__ void __launch_bounds__(512) k_rows(const char* src, unsigned long fby
   int pc = lane % LPR;
   if (MODE == 1) pc ^= (row * 5 + 3) & (LPR - 1);
   if (MODE == 3) pc ^= (row >> 1) & 3 & (LPR - 1);
+  if (MODE == 4) pc ^= (row >> 1) & 7 & (LPR - 1);
   const int col = pc * 16;
   const unsigned long rows_total = fbytes / (unsigned long)pitch;
   unsigned long r0 = ((unsigned long)blockIdx.x * 4096 + (unsigned long)wave * 64) & (rows_total - 1);
@@ -54,7 +56,7 @@ static void run(const char* src, unsigned long fbytes, int pitch, int ncu, int* 
   float ms = 0.f;
   hipEventElapsedTime(&ms, e0, e1);
   const double bytes = (double)grid * 8 * 1024 * iters * reps;
-  static const char* mn[] = {"linear", "xor-row", "out-of-range", "xor (r>>1)&3"};
+  static const char* mn[] = {"linear", "xor-row", "out-of-range", "xor (r>>1)&3", "xor (r>>1)&7"};
   printf("row %4d B pitch %5d B %-13s: %7.1f GB/s per CU (%.1f cycles per 1-KiB instruction at 2.4 GHz)\n", ROWB, pitch,
          mn[MODE], bytes / (ms * 1e-3) / 1e9 / ncu, 1024.0 / (bytes / (ms * 1e-3) / ncu / 2.4e9));
 }
@@ -72,6 +74,15 @@ int main() {
   run<64, 3>(src, f, 512, ncu, sink);
   run<64, 1>(src, f, 512, ncu, sink);
   run<64, 2>(src, f, 512, ncu, sink);
+  // 64-deep K-tiles: 8 rows x 128 B per instruction, and the 64-B rows beside them at each pitch
+  run<128, 0>(src, f, 128, ncu, sink);
+  run<128, 4>(src, f, 128, ncu, sink);
+  run<64, 3>(src, f, 128, ncu, sink);
+  run<128, 0>(src, f, 512, ncu, sink);
+  run<128, 4>(src, f, 512, ncu, sink);
+  run<128, 4>(src, f, 2048, ncu, sink);
+  run<64, 3>(src, f, 2048, ncu, sink);
+  run<128, 2>(src, f, 512, ncu, sink);
   run<256, 0>(src, f, 512, ncu, sink);
   run<256, 1>(src, f, 512, ncu, sink);
   run<256, 3>(src, f, 512, ncu, sink);
