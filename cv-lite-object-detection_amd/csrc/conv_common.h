@@ -2,6 +2,7 @@
 #pragma once
 #include "cvl_common.h"
 #include "bn_acc.h"
+#include <type_traits>
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -10,7 +11,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxSeg = CVL_CONV_MAX_SEG;
 
-// kernel variant of the last cvl_conv_igemm call on this host thread (cvl_conv_igemm_last_kernel)
+// kernel variant of the last cvl_conv_igemm call on this host thread (cvl_conv_igemm_last_kernel);
+// the forward / data-gradient family sets it from the launch's ConvPlan (conv_igemm.hip: conv_run)
 extern thread_local int g_cvl_conv_last_kernel;
 // K-tile depth (32 / 64) of the last X or P launch on this host thread (cvl_conv_igemm_last_ktile)
 extern thread_local int g_cvl_conv_last_ktile;
@@ -92,11 +94,6 @@ struct ConvArgs {
   const cvl_bf16* ymask;       // data gradient through a ReLU: outputs where ymask <= 0 stored as 0 (X32 SW only)
 };
 
-// cvl_conv_igemm_relu_mask: the ReLU output whose mask the next launch's epilogue may apply; a kernel
-// that applies it sets g_cvl_ymask_used (else the caller runs the separate ReLU backward)
-extern thread_local const void* g_cvl_ymask;
-extern thread_local int g_cvl_ymask_used;
-
 // cvl_probe_arm (probe.hip): the slot armed for the current cvl_conv_igemm call (taken at its entry;
 // take = clear it, so one armed slot times at most one launch)
 uint64_t* cvl_probe_current(bool take);
@@ -144,6 +141,72 @@ struct BnSumArgs {
   float hi;
   const cvl_bf16* y;      // residual unit: mask y > 0 (null: rebuilt from z)
 };
+
+// ---- forward / data-gradient dispatch (conv_dispatch.hip) ---------------------------------------
+// What a call offers beyond its descriptor.
+enum { CVL_BSUM_NONE = 0, CVL_BSUM_Z = 1, CVL_BSUM_Y = 2 };   // fused BN-backward sums: mask from bn(z) / from y
+struct ConvCallOpts {
+  bool bn_stats;            // BN statistics requested
+  int bsum;                 // fused BN-backward sums offered (CVL_BSUM_*)
+  bool ymask;               // a ReLU mask offered (cvl_conv_igemm_relu_mask)
+  size_t workspace_bytes;   // 0: no workspace
+};
+
+enum { CVL_PRE_NONE = 0, CVL_PRE_ZERO_GAPS = 1, CVL_PRE_S2DG3_PACK = 2 };   // pass before the launch
+
+// Everything the host decides for one call, computed once by conv_plan (host only, launches nothing,
+// the one reader of the family's cvl_dispatch_* / cvl_tune_* keys).  The launchers instantiate and
+// launch what it says and decide nothing.
+struct ConvPlan {
+  int kernel;               // CVL_CK_* family
+  int bn, bk;               // N-tile width, K-tile depth
+  bool dgrad;
+  bool sw;                  // register (SW) epilogue instead of the LDS C image
+  bool wres;                // H64: weights resident
+  bool prio, acc, stamps;   // L: s_setprio around the MFMA cluster; P: beta-accumulate form; H64: measurement stamps
+  int stages;               // H64 ring stages (2 / 3)
+  int bsum;                 // fused BN sums applied (CVL_BSUM_*; NONE when offered but not fusable)
+  bool ymask;               // the ReLU mask is applied in the epilogue
+  int splits, ksteps_per_split;
+  int grid;                 // workgroups (per split)
+  size_t workspace_bytes;   // workspace this plan uses (pack + split-K slabs)
+  int pre;                  // CVL_PRE_*
+  size_t pack_bytes;        // CVL_PRE_S2DG3_PACK: the sub-kernel packs at the head of the workspace
+  int dbg;                  // measurement builds: the kernel's ablation bits
+  cvl_conv_desc desc;       // the descriptor the kernel runs (a strided data gradient rewritten)
+  ConvArgs geo;             // its segment layout, dst_up / dst_w set, no pointers but the weights'
+};
+
+int conv_plan(const cvl_conv_desc* d, const ConvCallOpts& o, ConvPlan* p);
+size_t conv_plan_workspace_bound(const cvl_conv_desc* d);
+// splits / ksteps_per_split of `want` splits over nk K steps (no empty split)
+static inline void conv_plan_set_splits(ConvPlan* p, int nk, int want) {
+  p->ksteps_per_split = (nk + want - 1) / want;
+  p->splits = (nk + p->ksteps_per_split - 1) / p->ksteps_per_split;
+}
+// what the K-tile query reports: the depth of an X or P launch, else 0
+static inline int conv_plan_ktile(const ConvPlan& p) { return p.kernel == CVL_CK_X32 || p.kernel == CVL_CK_P ? p.bk : 0; }
+
+// the launchers: conv_igemm.hip (128-row kernel), conv_igemm_{l,x,h,p}.hip; return the launch status
+int launch_base(const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_l(const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_x(const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_h(const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_p(const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+
+// H64's geometry predicate (conv_igemm_h.hip, next to the halo geometry it tests); *halo_px: the
+// largest segment halo in pixels
+bool cvl_conv_h_fits(const cvl_conv_desc* d, const ConvArgs& a, int* halo_px);
+constexpr int kConvHWresCb = 2;             // H64 weights-resident form: channel blocks at most (WRES_CB)
+constexpr int kConvHStampWgs = 4096;        // H64 measurement stamps: workgroups at most (kHStampWgs)
+constexpr unsigned kConvBufRecords = 0x7fffffffu;   // buffer-resource bound of the X / H / P operand fetches
+
+// runtime bool -> template argument: with_bool(b, [&](auto B) { f<decltype(B)::value>(); })
+template <class F>
+static inline void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // destination row of GEMM row q (within image img) of segment S
 __device__ __forceinline__ long conv_dst_row(const ConvArgs& a, const ConvSeg& S, int img, int q) {

@@ -414,111 +414,26 @@ static int splitk_finish_launch(const ConvArgs& a, hipStream_t s) {
   return cvl_launch_status();
 }
 
-// split-K factor: only for grids that cannot fill the chip (small M, e.g. conv5 / c6 at 16x16)
-static inline int pick_ksplit(const ConvArgs& a, int BN_, int BK_) {
-  if (a.nseg != 1) return 1;
-  const int tiles = a.m_tiles * (a.Npad / BN_);
-  const int nk = a.K / BK_;
-  const int max_tiles = cvl_tune_int("CVL_KSPLIT_MAX_TILES", 192);
-  const int target = cvl_tune_int("CVL_KSPLIT_TARGET", 384);   // workgroups a split launch aims for
-  // short-K small launches split too (>= 4 K steps, >= 2 per split): the hourglass's 16x16 / 32x32
-  // levels at bs 8, CenterNet 546 -> 554 img/s (8 / 4: the previous rule; 2 / 1 and a 768 target: less)
-  const int min_nk = cvl_dispatch_int("ksplit_min_nk", 4);     // K steps a split needs at least
-  if (tiles >= max_tiles || nk < min_nk) return 1;
-  int s = (target + tiles - 1) / tiles;
-  const int per = cvl_tune_int("CVL_KSPLIT_MIN_PER", 2);       // K steps per split at least
-  if (s > nk / per) s = nk / per;
-  return s < 1 ? 1 : s;
-}
-
 template <int BN, int BK>
-int launch_bn_bk(const ConvArgs& a0, bool dgrad, hipStream_t s) {
-  ConvArgs a = a0;
-  if (a.splits > 1) {
-    const int nk = a.K / BK;
-    a.ksteps_per_split = (nk + a.splits - 1) / a.splits;
-    a.splits = (nk + a.ksteps_per_split - 1) / a.ksteps_per_split;
-  }
+void launch_bn_bk(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
   dim3 grid(a.m_tiles, a.Npad / BN, a.splits);
-  if (dgrad) hipLaunchKernelGGL((conv_igemm_kernel<BN, BK, true>), grid, dim3(NT), 0, s, a);
-  else hipLaunchKernelGGL((conv_igemm_kernel<BN, BK, false>), grid, dim3(NT), 0, s, a);
-  int st = cvl_launch_status();
-  if (st || a.splits <= 1) return st;
-  return splitk_finish_launch(a, s);
+  with_bool(p.dgrad, [&](auto DG) {
+    hipLaunchKernelGGL((conv_igemm_kernel<BN, BK, decltype(DG)::value>), grid, dim3(NT), 0, s, a);
+  });
 }
 
+// (plain `if`: the 128-wide tile keeps its 128-deep instantiation, which is never planned)
 template <int BN>
-int launch_bn(const ConvArgs& a, bool dgrad, hipStream_t s) {
-  // narrow outputs (the FCOS / RetinaNet heads, N <= 64): 128-deep K steps -- twice the bytes per
-  // register-staged load round in flight (these launches are bound by the load latency, not MFMA)
-  if (BN <= 64 && a.Cin % 128 == 0 && cvl_dispatch_int("base_bk128", 1)) return launch_bn_bk<BN, 128>(a, dgrad, s);
-  if (a.Cin % 64 == 0) return launch_bn_bk<BN, 64>(a, dgrad, s);
-  return launch_bn_bk<BN, 32>(a, dgrad, s);
+void launch_bn(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (BN <= 64 && p.bk == 128) launch_bn_bk<BN, 128>(p, a, s);
+  else if (p.bk == 64) launch_bn_bk<BN, 64>(p, a, s);
+  else launch_bn_bk<BN, 32>(p, a, s);
 }
-
-static inline int pick_bn(int npad) { return npad % 128 == 0 ? 128 : (npad % 64 == 0 ? 64 : 32); }
 
 }  // namespace
 
-int cvl_conv_igemm_l(const cvl_conv_desc* d, int dst_up, int dst_w, const void* src, void* dst, acc_u64* bn_stats,
-                     hipStream_t s, const BnSumArgs* bsum = nullptr, void* workspace = nullptr,
-                     size_t workspace_bytes = 0);
-size_t cvl_conv_h_workspace(const cvl_conv_desc* d, const ConvArgs& a);
-
-// the split-K finishing pass of a single-segment launch whose partial slabs a.slab holds (used by
-// the halo kernel conv_igemm_h.hip as well)
-int cvl_conv_splitk_finish(const ConvArgs& a, hipStream_t s) { return splitk_finish_launch(a, s); }
-
-// 1x1 strided data-gradient: only every stride-th dX pixel receives a gradient, so instead of a
-// DGRAD gather that finds no valid tap for (s^2-1)/s^2 of the rows, run a dense 1x1 GEMM over the
-// dY pixels whose epilogue writes row (y, x) to dX pixel (y*s, x*s); the other pixels are zeroed
-// (beta == 0) or keep their accumulated value (beta != 0: they receive + 0).
-static bool s2dgrad_transform(const cvl_conv_desc* d, cvl_conv_desc* out, int* up, int* upw) {
-  if (d->mode != CVL_CONV_DGRAD || d->KH != 1 || d->KW != 1 || d->stride < 2 || d->nseg != 1 ||
-      d->pad_t != 0 || d->pad_l != 0 || d->relu_in || cvl_tune_flag("CVL_CONV_NO_S2DG"))
-    return false;
-  const cvl_conv_seg& q = d->seg[0];
-  if ((q.Hs - 1) * d->stride >= q.Hr || (q.Ws - 1) * d->stride >= q.Wr) return false;
-  *out = *d;
-  out->mode = CVL_CONV_FWD;
-  out->stride = 1;
-  out->seg[0].Hr = q.Hs;
-  out->seg[0].Wr = q.Ws;
-  *up = d->stride;
-  *upw = q.Wr;
-  return true;
-}
-
-// 3x3 / stride-2 data gradient with zero leading pads on an even map (TF 'same': the FPN's P6 / P7
-// convs, fcos.py:66-72; conv2d_backprop_input of a stride-2 kernel) as ONE 4-segment forward launch
-// over the dY map.  Input pixel (2k + py, 2k' + px) receives dY[k - 1 + r'][k' - 1 + s'] through
-// the 2x2 sub-kernel of its parity class: tap r' = 1 is r = 0 (py even) / r = 1 (odd), r' = 0 is
-// r = 2 (even) / nothing (odd) -- the same along x.  The four sub-kernels are gathered from the
-// dgrad pack into the workspace (missing taps zero) and the results scatter by dst_up = 2 at offset
-// py * W + px.  K = 4 * Cout instead of the 9 * Cout of the direct form, most of whose taps meet dY
-// rows that do not exist at the pixel's parity (c6 dgrad 256 -> 2048 @ 16^2: 82 us).
-static int grid_for_n(long n) {
-  const long b = (n + NT - 1) / NT;
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
-
-static bool s2dgrad3_ok(const cvl_conv_desc* d) {
-  if (!d || d->mode != CVL_CONV_DGRAD || d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad_t || d->pad_l ||
-      d->nseg != 1 || d->relu_in || d->prec != CVL_PREC_BF16 || d->Cin % 32 || d->Npad % 32 ||
-      cvl_dispatch_flag("no_s2dg3"))
-    return false;
-  const cvl_conv_seg& q = d->seg[0];
-  // small maps (P7's 8x8 at bs 16: 1024 rows) keep the direct form, whose split-K fills the GPU
-  // (the 4-segment launch has no split-K: 16 workgroups, 22 -> 37 us)
-  return q.Hr == 2 * q.Hs && q.Wr == 2 * q.Ws && q.w &&
-         (long)d->B * q.Hr * q.Wr >= cvl_dispatch_int("s2dg3_min_rows", 4096);
-}
-
-static size_t s2dgrad3_pack_bytes(const cvl_conv_desc* d) {
-  return ((size_t)4 * d->Npad * 4 * d->Cin * sizeof(cvl_bf16) + 255) / 256 * 256;
-}
-
-// sub[cls][n][t' = 2 r' + s'][c] from wd[n][(3 r + s) * Cin + c], 16-B chunks
+// sub[cls][n][t' = 2 r' + s'][c] from wd[n][(3 r + s) * Cin + c], 16-B chunks: the four 2x2
+// sub-kernels of a 3x3 / stride-2 data gradient (conv_dispatch.hip: s2dgrad3_ok)
 __global__ void s2dgrad3_pack_kernel(const cvl_bf16* __restrict__ wd, cvl_bf16* __restrict__ sub, int Npad, int Cin) {
   const int c8n = Cin / 8;
   const long total = 16L * Npad * c8n;
@@ -535,27 +450,6 @@ __global__ void s2dgrad3_pack_kernel(const cvl_bf16* __restrict__ wd, cvl_bf16* 
     if (r >= 0 && sx >= 0) v = *reinterpret_cast<const s16x8*>(wd + (long)n * 9 * Cin + (r * 3 + sx) * Cin + c8 * 8);
     *reinterpret_cast<s16x8*>(sub + i * 8) = v;
   }
-}
-
-// the 4-segment forward descriptor over the packs at `sub`
-static cvl_conv_desc s2dgrad3_desc(const cvl_conv_desc* d, const cvl_bf16* sub) {
-  cvl_conv_desc dd = *d;
-  const cvl_conv_seg q = d->seg[0];
-  dd.mode = CVL_CONV_FWD;
-  dd.KH = dd.KW = 2;
-  dd.stride = 1;
-  dd.pad_t = dd.pad_l = 1;
-  dd.nseg = 4;
-  for (int cls = 0; cls < 4; ++cls) {
-    cvl_conv_seg& g = dd.seg[cls];
-    g = q;
-    g.Hr = q.Hs;
-    g.Wr = q.Ws;
-    g.w = sub + (size_t)cls * d->Npad * 4 * d->Cin;
-    g.bias = nullptr;
-    g.dst_base = q.dst_base + (long)(cls >> 1) * q.Wr + (cls & 1);
-  }
-  return dd;
 }
 
 // the pixels a strided data gradient's scatter does not reach, zeroed: one block row per (image,
@@ -578,13 +472,98 @@ __global__ void zero_gaps_kernel(void* dst, int is_f32, long dst_base, long dst_
   }
 }
 
+namespace {
+
+// the pass a plan asks for before its launch (d: the caller's descriptor)
+int pre_pass(const ConvPlan& p, const cvl_conv_desc* d, void* dst, void* workspace, hipStream_t s) {
+  if (p.pre == CVL_PRE_S2DG3_PACK) {
+    const long b = (16L * d->Npad * (d->Cin / 8) + NT - 1) / NT;
+    hipLaunchKernelGGL(s2dgrad3_pack_kernel, dim3((int)(b > 4096 ? 4096 : (b < 1 ? 1 : b))), dim3(NT), 0, s,
+                       reinterpret_cast<const cvl_bf16*>(d->seg[0].w), reinterpret_cast<cvl_bf16*>(workspace), d->Npad,
+                       d->Cin);
+  } else if (p.pre == CVL_PRE_ZERO_GAPS) {
+    const cvl_conv_seg& q = d->seg[0];
+    const long line = (long)q.Wr * (d->dst_f32 ? d->n_store : d->n_store / 8);
+    const int bx = (int)((line + NT - 1) / NT);
+    const int by = d->B * q.Hr < 65535 ? d->B * q.Hr : 65535;
+    hipLaunchKernelGGL(zero_gaps_kernel, dim3(bx < 1 ? 1 : bx, by), dim3(NT), 0, s, dst, d->dst_f32, q.dst_base,
+                       q.dst_img, d->ld_dst, d->dst_coff, d->n_store, d->B, q.Hr, q.Wr, d->stride);
+  } else {
+    return CVL_OK;
+  }
+  return cvl_launch_status();
+}
+
+// what a call hands over beside its descriptor
+struct ConvIo {
+  const void* src;
+  void* dst;
+  acc_u64* stats;
+  const BnSumArgs* bsum;     // read when the plan fuses the BN sums
+  const void* ymask;         // read when the plan applies the ReLU mask
+  void* workspace;
+};
+
+// The kernel arguments of a planned call: the plan's layout plus the call's pointers.
+void fill_args(const ConvPlan& p, const ConvIo& io, ConvArgs* a) {
+  *a = p.geo;
+  a->src = reinterpret_cast<const cvl_bf16*>(io.src);
+  a->dst = io.dst;
+  a->stats = io.stats;
+  if (p.bsum) {
+    const BnSumArgs& b = *io.bsum;
+    a->bz = b.z; a->bmr = b.mr; a->bga = b.gamma; a->bbe = b.beta; a->bsum = b.sums; a->bhi = b.hi;
+    a->by = b.y;
+  }
+  if (p.ymask) a->ymask = reinterpret_cast<const cvl_bf16*>(io.ymask);
+  // bench.py's in-step timing: the tower kernel takes the call's armed slot
+  if (p.kernel == CVL_CK_X32) a->probe = reinterpret_cast<unsigned long long*>(cvl_probe_current(true));
+  a->dbg = p.dbg;
+  a->splits = p.splits;
+  a->ksteps_per_split = p.ksteps_per_split;
+  char* ws = reinterpret_cast<char*>(io.workspace);
+  if (p.splits > 1) a->slab = reinterpret_cast<float*>(ws + p.pack_bytes);
+  if (p.pre == CVL_PRE_S2DG3_PACK)       // the four sub-kernel packs the pre-pass wrote
+    for (int i = 0; i < kMaxSeg; ++i)
+      a->seg[i].w = reinterpret_cast<const cvl_bf16*>(ws) + (size_t)(i < a->nseg ? i : 0) * a->Npad * a->K;
+}
+
+}  // namespace
+
 thread_local int g_cvl_conv_last_kernel = CVL_CK_NONE;
 thread_local int g_cvl_conv_last_ktile = 0;
-thread_local const void* g_cvl_ymask = nullptr;
-thread_local int g_cvl_ymask_used = 0;
 
 extern "C" int cvl_conv_igemm_last_kernel(void) { return g_cvl_conv_last_kernel; }
 extern "C" int cvl_conv_igemm_last_ktile(void) { return g_cvl_conv_last_ktile; }
+
+// Launches the 128-row kernel as planned.
+int launch_base(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.bn == 128) launch_bn<128>(p, a, s);
+  else if (p.bn == 64) launch_bn<64>(p, a, s);
+  else launch_bn<32>(p, a, s);
+  return cvl_launch_status();
+}
+
+namespace {
+// A planned call: optional pre-pass, the launch, optional split-K finish.
+int conv_run(const ConvPlan& p, const cvl_conv_desc* d, const ConvIo& io, hipStream_t s) {
+  int st = pre_pass(p, d, io.dst, io.workspace, s);
+  if (st) return st;
+  ConvArgs a;
+  fill_args(p, io, &a);
+  switch (p.kernel) {
+    case CVL_CK_P: st = launch_p(p, a, s); break;
+    case CVL_CK_X32: st = launch_x(p, a, s); break;
+    case CVL_CK_H64: st = launch_h(p, a, s); break;
+    case CVL_CK_L64: case CVL_CK_L128: case CVL_CK_L256: st = launch_l(p, a, s); break;
+    default: st = launch_base(p, a, s); break;
+  }
+  g_cvl_conv_last_kernel = p.kernel;
+  g_cvl_conv_last_ktile = conv_plan_ktile(p);
+  if (st || p.splits <= 1) return st;
+  return splitk_finish_launch(a, s);
+}
+}  // namespace
 
 extern "C" const char* cvl_conv_kernel_name(int code) {
   switch (code) {
@@ -609,62 +588,46 @@ extern "C" const char* cvl_conv_kernel_name(int code) {
 }
 
 int cvl_conv_f32(const cvl_conv_desc* d, const void* src, void* dst, acc_u64* bn_stats, hipStream_t s);
+int cvl_relu_backward(const void* dy, const void* y, void* dx, long n, float beta, cvl_stream_t stream);
 
 extern "C" size_t cvl_conv_igemm_workspace_size(const cvl_conv_desc* d) {
-  if (d && d->prec == CVL_PREC_F32) return 16;
-  if (s2dgrad3_ok(d)) {            // the sub-kernel packs, then the 4-segment launch's own needs
-    const cvl_conv_desc dd = s2dgrad3_desc(d, reinterpret_cast<const cvl_bf16*>(16));
-    return s2dgrad3_pack_bytes(d) + cvl_conv_igemm_workspace_size(&dd);
-  }
-  cvl_conv_desc dd;
-  int up = 1, upw = 0;
-  if (s2dgrad_transform(d, &dd, &up, &upw)) d = &dd;
-  ConvArgs a;
-  if (cvl_conv_prepare(d, BM, &a)) return 0;
-  const int sp = pick_ksplit(a, pick_bn(a.Npad), a.Cin % 64 == 0 ? 64 : 32);
-  size_t n = sp > 1 ? (size_t)sp * a.m_total * a.Npad * sizeof(float) : 16;
-  ConvArgs a256;                                   // the halo kernel's split-K slabs (256-row tiles)
-  if (cvl_conv_prepare(d, 256, &a256) == CVL_OK) {
-    const size_t h = cvl_conv_h_workspace(d, a256);
-    n = h > n ? h : n;
-  }
-  return n;
+  if (!d) return 0;
+  if (d->prec == CVL_PREC_F32) return 16;
+  return conv_plan_workspace_bound(d);
 }
-
-namespace {
-int conv_igemm_call(const cvl_conv_desc* d, const void* src, void* dst, uint64_t* bn_stats_acc, void* workspace,
-                    size_t workspace_bytes, cvl_stream_t stream);
-}  // namespace
 
 extern "C" int cvl_conv_igemm(const cvl_conv_desc* d, const void* src, void* dst, uint64_t* bn_stats_acc,
                               void* workspace, size_t workspace_bytes, cvl_stream_t stream) {
+  CVL_CHECK_ARG(d);
+  acc_u64* bn_stats = reinterpret_cast<acc_u64*>(bn_stats_acc);
+  if (d->prec == CVL_PREC_F32) return cvl_conv_f32(d, src, dst, bn_stats, (hipStream_t)stream);    // parity mode
+  ConvPlan p;
+  const int st = conv_plan(d, ConvCallOpts{bn_stats != nullptr, CVL_BSUM_NONE, false, workspace ? workspace_bytes : 0}, &p);
+  if (st) return st;
+  CVL_CHECK_ARG(src && dst);
   cvl_probe_enter_call();            // an armed probe slot belongs to this call and leaves with it
-  const int st = conv_igemm_call(d, src, dst, bn_stats_acc, workspace, workspace_bytes, stream);
+  const int rst = conv_run(p, d, ConvIo{src, dst, bn_stats, nullptr, nullptr, workspace}, (hipStream_t)stream);
   cvl_probe_leave_call();
-  return st;
+  return rst;
 }
-
-int cvl_relu_backward(const void* dy, const void* y, void* dx, long n, float beta, cvl_stream_t stream);
 
 // A data gradient through a ReLU (FPNDetector.trunk_backward: the heads' data gradients into the
 // towers' ReLU outputs, fcos.py:16-27 / 76-101): dst = dgrad(src) * (y > 0), y laid out as dst.  The
 // X32 register epilogue applies the mask; any other kernel's launch is followed by the separate
-// ReLU backward (then dst must be dense: ld_dst == n_store, dst_coff 0).  Bit-identical to
-// cvl_conv_igemm + cvl_relu_backward either way.
+// ReLU backward (then dst must be dense: ld_dst == n_store, dst_coff 0 -- checked before anything
+// is launched).  Bit-identical to cvl_conv_igemm + cvl_relu_backward either way.
 extern "C" int cvl_conv_igemm_relu_mask(const cvl_conv_desc* d, const void* src, void* dst, const void* y,
                                         void* workspace, size_t workspace_bytes, cvl_stream_t stream) {
   CVL_CHECK_ARG(d && src && dst && y && d->mode == CVL_CONV_DGRAD && d->prec == CVL_PREC_BF16 && !d->dst_f32 &&
                 d->beta == 0.f && !d->relu_out);
-  g_cvl_ymask = cvl_dispatch_flag("no_relu_mask_fuse") ? nullptr : y;
-  g_cvl_ymask_used = 0;
+  ConvPlan p;
+  int st = conv_plan(d, ConvCallOpts{false, CVL_BSUM_NONE, true, workspace ? workspace_bytes : 0}, &p);
+  if (st) return st;
+  if (!p.ymask) CVL_CHECK_ARG(d->ld_dst == d->n_store && d->dst_coff == 0);
   cvl_probe_enter_call();
-  const int st = conv_igemm_call(d, src, dst, nullptr, workspace, workspace_bytes, stream);
+  st = conv_run(p, d, ConvIo{src, dst, nullptr, nullptr, y, workspace}, (hipStream_t)stream);
   cvl_probe_leave_call();
-  const int used = g_cvl_ymask_used;
-  g_cvl_ymask = nullptr;
-  g_cvl_ymask_used = 0;
-  if (st || used) return st;
-  CVL_CHECK_ARG(d->ld_dst == d->n_store && d->dst_coff == 0);
+  if (st || p.ymask) return st;
   long rows = 0;
   for (int i = 0; i < d->nseg; ++i) {
     const long e = d->seg[i].dst_base + (long)d->B * (d->seg[i].dst_img ? d->seg[i].dst_img : (long)d->seg[i].Hr * d->seg[i].Wr);
@@ -674,120 +637,40 @@ extern "C" int cvl_conv_igemm_relu_mask(const cvl_conv_desc* d, const void* src,
 }
 
 namespace {
-int conv_igemm_call(const cvl_conv_desc* d, const void* src, void* dst, uint64_t* bn_stats_acc, void* workspace,
-                    size_t workspace_bytes, cvl_stream_t stream) {
-  acc_u64* bn_stats = reinterpret_cast<acc_u64*>(bn_stats_acc);
-  hipStream_t s = (hipStream_t)stream;
-  g_cvl_conv_last_kernel = CVL_CK_NONE;
-  g_cvl_conv_last_ktile = 0;
-  CVL_CHECK_ARG(d);
-  if (d->prec == CVL_PREC_F32) return cvl_conv_f32(d, src, dst, bn_stats, s);    // parity mode
-  CVL_CHECK_ARG(d->prec == CVL_PREC_BF16);
-  cvl_conv_desc dd;
-  int up = 1, upw = 0;
-  if (s2dgrad3_ok(d) && workspace && workspace_bytes >= s2dgrad3_pack_bytes(d)) {
-    CVL_CHECK_ARG(src && dst && !bn_stats);
-    CVL_CHECK_ARG(d->dst_f32 || (d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->n_store % 8 == 0));
-    cvl_bf16* sub = reinterpret_cast<cvl_bf16*>(workspace);
-    const long total = 16L * d->Npad * (d->Cin / 8);
-    hipLaunchKernelGGL(s2dgrad3_pack_kernel, dim3(grid_for_n(total)), dim3(NT), 0, s,
-                       reinterpret_cast<const cvl_bf16*>(d->seg[0].w), sub, d->Npad, d->Cin);
-    const int pst = cvl_launch_status();
-    if (pst) return pst;
-    const size_t pk = s2dgrad3_pack_bytes(d);
-    up = 2;
-    upw = d->seg[0].Wr;
-    dd = s2dgrad3_desc(d, sub);
-    d = &dd;
-    workspace = reinterpret_cast<char*>(workspace) + pk;
-    workspace_bytes -= pk;
-  } else if (s2dgrad_transform(d, &dd, &up, &upw)) {
-    CVL_CHECK_ARG(src && dst && !bn_stats);
-    CVL_CHECK_ARG(d->dst_f32 || (d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->n_store % 8 == 0));
-    if (d->beta == 0.f) {
-      const cvl_conv_seg& q = d->seg[0];
-      const long line = (long)q.Wr * (d->dst_f32 ? d->n_store : d->n_store / 8);
-      CVL_CHECK_ARG(line < (1l << 31) && (long)d->B * q.Hr < (1l << 31));
-      const int bx = (int)((line + NT - 1) / NT);
-      const int by = d->B * q.Hr < 65535 ? d->B * q.Hr : 65535;
-      hipLaunchKernelGGL(zero_gaps_kernel, dim3(bx < 1 ? 1 : bx, by), dim3(NT), 0, s, dst, d->dst_f32,
-                         q.dst_base, q.dst_img, d->ld_dst, d->dst_coff, d->n_store,
-                         d->B, q.Hr, q.Wr, d->stride);
-      const int zst = cvl_launch_status();
-      if (zst) return zst;
-    }
-    d = &dd;
-  }
-  ConvArgs a;
-  int st = cvl_conv_prepare(d, BM, &a);
+// The two fused BN-sums entries: plan with the sums offered; where no kernel can fuse them, plan
+// the plain data gradient (*fused = 0: the caller then runs the two-pass BN backward).
+int dgrad_bnsum_call(const cvl_conv_desc* d, const void* src, void* dst, int form, const BnSumArgs& b, int32_t* fused,
+                     void* workspace, size_t workspace_bytes, cvl_stream_t stream) {
+  *fused = 0;
+  if (d->prec == CVL_PREC_F32) return cvl_conv_f32(d, src, dst, nullptr, (hipStream_t)stream);    // parity mode
+  const size_t ws = workspace ? workspace_bytes : 0;
+  ConvPlan p;
+  int st = conv_plan(d, ConvCallOpts{false, form, false, ws}, &p);
   if (st) return st;
-  a.dst_up = up;
-  a.dst_w = upw;
+  const bool fuse = p.kernel != CVL_CK_NONE && src && dst;
+  if (!fuse && (st = conv_plan(d, ConvCallOpts{false, CVL_BSUM_NONE, false, ws}, &p))) return st;
   CVL_CHECK_ARG(src && dst);
-  CVL_CHECK_ARG(d->Cin % 32 == 0 && a.Npad % 32 == 0);
-  if (!d->dst_f32) CVL_CHECK_ARG(d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->n_store % 8 == 0);
-  if (bn_stats) {
-    for (int i = 0; i < a.nseg; ++i) {
-      const int hw = a.seg[i].Hr * a.seg[i].Wr;
-      CVL_CHECK_ARG(hw % BM == 0 || hw % 4 == 0);   // quads of rows never straddle images
-    }
-  }
-  {
-    const int lst = cvl_conv_igemm_l(d, up, upw, src, dst, bn_stats, s, nullptr, workspace, workspace_bytes);
-    if (lst >= 0) return lst;          // the 256-row LDS-DMA kernel took the launch
-  }
-  a.src = reinterpret_cast<const cvl_bf16*>(src);
-  a.dst = dst;
-  a.stats = bn_stats;
-  const int bn = pick_bn(a.Npad);
-  const int sp = pick_ksplit(a, bn, a.Cin % 64 == 0 ? 64 : 32);
-  if (sp > 1 && workspace && (d->n_store / 8 <= NT) && workspace_bytes >= (size_t)sp * a.m_total * a.Npad * sizeof(float) &&
-      d->n_store % 8 == 0 && d->dst_coff % 8 == 0 && (d->dst_f32 || d->ld_dst % 8 == 0)) {
-    a.splits = sp;
-    a.slab = reinterpret_cast<float*>(workspace);
-  }
-  const bool dg = d->mode == CVL_CONV_DGRAD;
-  g_cvl_conv_last_kernel = a.splits > 1 ? CVL_CK_BASE_SPLITK : CVL_CK_BASE;
-  if (bn == 128) return launch_bn<128>(a, dg, s);
-  if (bn == 64) return launch_bn<64>(a, dg, s);
-  return launch_bn<32>(a, dg, s);
+  // (an armed probe slot belongs to the next plain call: a fused launch leaves it armed)
+  if (!fuse) cvl_probe_enter_call();
+  st = conv_run(p, d, ConvIo{src, dst, nullptr, &b, nullptr, workspace}, (hipStream_t)stream);
+  if (!fuse) cvl_probe_leave_call();
+  *fused = fuse && st == CVL_OK ? 1 : 0;
+  return st;
 }
 }  // namespace
 
 // Data gradient whose epilogue also forms the first pass of the NEXT BN's backward (the dgrad
 // result is dy of a BN -> ReLU unit without a residual): sums[img][c] += (sum g, sum g*xhat).
-// Taken when the 256-row LDS-DMA kernel runs the launch with one image per tile; otherwise the
+// Taken when a 256-row LDS-DMA kernel runs the launch with one image per tile; otherwise the
 // plain data gradient runs and *fused = 0 (the caller then runs the two-pass BN backward).
 extern "C" int cvl_conv_igemm_dgrad_bnsum(const cvl_conv_desc* d, const void* src, void* dst, const void* z,
                                           const float* mean_rstd, const float* gamma, const float* beta, float act_hi,
                                           uint64_t* sums, int32_t* fused, void* workspace, size_t workspace_bytes,
                                           cvl_stream_t stream) {
   CVL_CHECK_ARG(d && fused && z && mean_rstd && gamma && beta && sums);
-  *fused = 0;
-  if (!cvl_tune_flag("CVL_NO_BNSUM_FUSE") && d->prec == CVL_PREC_BF16 && d->mode == CVL_CONV_DGRAD &&
-      // (CVL_BNSUM_MIN_HW: A/B knob; unlike the residual form this one pays on every stage -- a 64x64
-      // floor cost 0.6 %, 32x32 was neutral)
-      !d->dst_f32 && d->beta == 0.f && (long)d->seg[0].Hr * d->seg[0].Wr >= cvl_tune_int("CVL_BNSUM_MIN_HW", 0) &&
-      d->Cin % 32 == 0 && d->Npad % 32 == 0 && d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->n_store % 8 == 0 &&
-      src && dst) {
-    cvl_conv_desc dd;
-    int up = 1, upw = 0;
-    if (!s2dgrad_transform(d, &dd, &up, &upw)) {
-      ConvArgs chk;
-      if (cvl_conv_prepare(d, BM, &chk) == CVL_OK) {
-        const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta,
-                          reinterpret_cast<acc_u64*>(sums), act_hi};
-        g_cvl_conv_last_kernel = CVL_CK_NONE;
-        const int lst = cvl_conv_igemm_l(d, 1, 0, src, dst, nullptr, (hipStream_t)stream, &b, workspace,
-                                         workspace_bytes);
-        if (lst >= 0) {
-          *fused = lst == CVL_OK ? 1 : 0;
-          return lst;
-        }
-      }
-    }
-  }
-  return cvl_conv_igemm(d, src, dst, nullptr, workspace, workspace_bytes, stream);
+  const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
+                    act_hi, nullptr};
+  return dgrad_bnsum_call(d, src, dst, CVL_BSUM_Z, b, fused, workspace, workspace_bytes, stream);
 }
 
 // The residual-unit form: the dgrad result, accumulated into dst with d->beta (the block-input
@@ -799,40 +682,7 @@ extern "C" int cvl_conv_igemm_dgrad_bnsum_res(const cvl_conv_desc* d, const void
                                               const float* beta, uint64_t* sums, int32_t* fused, void* workspace,
                                               size_t workspace_bytes, cvl_stream_t stream) {
   CVL_CHECK_ARG(d && fused && y && z && mean_rstd && gamma && beta && sums);
-  *fused = 0;
-  if (!cvl_tune_flag("CVL_NO_BNSUM_FUSE") && !cvl_tune_flag("CVL_NO_BNSUM_RES") && d->prec == CVL_PREC_BF16 &&
-      d->mode == CVL_CONV_DGRAD && !d->dst_f32 && d->beta != 0.f && d->KH == 1 && d->KW == 1 &&
-      (d->stride == 1 || !cvl_dispatch_flag("no_bnsum_res_s2")) &&
-      // map-size floor (dispatch knob bnsum_res_min_hw): 4096 kept conv4_x / conv5_x on the plain
-      // launch + separate pass in round 5; after round 6's kernel changes 256 (all ResNet-50 stages at
-      // 512 px) wins, FCOS step same box 1381.1-1382.8 -> 1385.2-1388.6 img/s over 6 alternating runs
-      (long)d->seg[0].Hr * d->seg[0].Wr >= cvl_dispatch_int("bnsum_res_min_hw", 256) &&
-      d->Cin % 32 == 0 && d->Npad % 32 == 0 && d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->n_store % 8 == 0 &&
-      src && dst) {
-    // a strided 1x1 data gradient (a stage's first block accumulating onto its shortcut's) runs as the
-    // dense GEMM over the dY grid with the scatter (dst_up); it accumulates (beta 1), so the gaps keep
-    // the zeros the first launch wrote and contribute nothing to the sums
-    cvl_conv_desc dd;
-    int up = 1, upw = 0;
-    const cvl_conv_desc* dp = d;
-    bool ok = true;
-    if (d->stride != 1) {
-      ok = s2dgrad_transform(d, &dd, &up, &upw);
-      dp = &dd;
-    }
-    ConvArgs chk;
-    if (ok && cvl_conv_prepare(dp, BM, &chk) == CVL_OK) {
-      BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
-                  INFINITY};
-      b.y = reinterpret_cast<const cvl_bf16*>(y);
-      g_cvl_conv_last_kernel = CVL_CK_NONE;
-      const int lst = cvl_conv_igemm_l(dp, up, upw, src, dst, nullptr, (hipStream_t)stream, &b, workspace,
-                                       workspace_bytes);
-      if (lst >= 0) {
-        *fused = lst == CVL_OK ? 1 : 0;
-        return lst;
-      }
-    }
-  }
-  return cvl_conv_igemm(d, src, dst, nullptr, workspace, workspace_bytes, stream);
+  const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
+                    INFINITY, reinterpret_cast<const cvl_bf16*>(y)};
+  return dgrad_bnsum_call(d, src, dst, CVL_BSUM_Y, b, fused, workspace, workspace_bytes, stream);
 }

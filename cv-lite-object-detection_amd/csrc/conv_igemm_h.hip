@@ -657,9 +657,40 @@ __global__ void __launch_bounds__(NT) conv_igemm_h_kernel(ConvArgs a) {
   }
 }
 
-}  // namespace
+static_assert(WRES_CB == kConvHWresCb && HPX >= 512, "conv_dispatch.hip plans with these");
 
-int cvl_conv_splitk_finish(const ConvArgs& a, hipStream_t s);
+// 64-wide tiles: weights resident or not, SW or C-image epilogue, stamped (measurement builds) or not
+template <bool DG, bool BS, bool ST>
+void h_launch64(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid, 1, p.splits);
+  with_bool(p.wres, [&](auto WR) {
+    with_bool(p.sw, [&](auto SW) {
+      hipLaunchKernelGGL((conv_igemm_h_kernel<DG, BS, decltype(WR)::value, ST, decltype(SW)::value>), grid, dim3(NT), 0,
+                         s, a);
+    });
+  });
+}
+
+// 32-wide tiles: two or three ring stages
+template <bool DG, bool BS, bool SW>
+void h_launch32(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.stages == 3) hipLaunchKernelGGL((conv_igemm_h_kernel<DG, BS, false, false, SW, 32, 3>), dim3(p.grid), dim3(NT), 0, s, a);
+  else hipLaunchKernelGGL((conv_igemm_h_kernel<DG, BS, false, false, SW, 32>), dim3(p.grid), dim3(NT), 0, s, a);
+}
+
+// forward / data gradient / data gradient with the fused BN sums (no fused sums on a forward)
+template <bool ST>
+void h_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.bn == 32 && !p.sw) h_launch32<false, false, false>(p, a, s);       // Npad 32: the FCOS heads' forward
+  else if (p.bn == 32 && p.dgrad && p.bsum) h_launch32<true, true, true>(p, a, s);
+  else if (p.bn == 32 && p.dgrad) h_launch32<true, false, true>(p, a, s);
+  else if (p.bn == 32) h_launch32<false, false, true>(p, a, s);
+  else if (p.dgrad && p.bsum) h_launch64<true, true, ST>(p, a, s);
+  else if (p.dgrad) h_launch64<true, false, ST>(p, a, s);
+  else h_launch64<false, false, ST>(p, a, s);
+}
+
+}  // namespace
 
 #ifdef CVL_MEASURE
 int g_h_stamp_grid = 0;
@@ -680,7 +711,9 @@ extern "C" int cvl_debug_h_stamps(uint64_t* host, int max_wgs) {
 
 // Geometry H64 covers: 3x3, stride 1, pad 1, source map = output map, every segment's 256-row tiles
 // whole image rows (W | 256, H*W % 256 == 0) or whole images (H*W | 256), halo within HPX pixels.
-bool cvl_conv_h_fits(const cvl_conv_desc* d, const ConvArgs& a) {
+// *halo_px: the largest segment's halo in pixels (three ring stages fit up to 512).
+bool cvl_conv_h_fits(const cvl_conv_desc* d, const ConvArgs& a, int* halo_px) {
+  *halo_px = 0;
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || a.Cin % BK ||
       (a.Npad % BN && a.Npad != 32) || a.relu_in || a.dst_up != 1)
     return false;
@@ -693,147 +726,24 @@ bool cvl_conv_h_fits(const cvl_conv_desc* d, const ConvArgs& a) {
     if (HW >= BM ? (BM % W || HW % BM) : (BM % HW)) return false;
     const HGeo g = h_geo(q.Hr, W);
     if (g.mx * g.my * (g.whole ? HW : BM) != BM || g.rows * g.pitch > HPX) return false;
+    if (g.rows * g.pitch > *halo_px) *halo_px = g.rows * g.pitch;
     const long src_bytes = (q.src_base + (long)a.B * q.src_img) * a.Cin * 2;
     if (src_bytes >= (long)kRecords - 65536) return false;
   }
   return (long)a.Npad * a.K * 2 < (long)kRecords;
 }
 
-// Runs the launch on H64 (called by cvl_conv_igemm_l for 3x3 launches it would give 64/128-wide
-// tiles); -1 when it does not apply.  `slab` / `slab_bytes`: the caller's split-K workspace (may be
-// null: no split).
-int cvl_conv_igemm_h(const cvl_conv_desc* d, const ConvArgs& a0, hipStream_t s, void* slab, size_t slab_bytes) {
-  if (cvl_dispatch_flag("no_h") || !cvl_conv_h_fits(d, a0)) return -1;
-  ConvArgs a = a0;
-  const bool dg = d->mode == CVL_CONV_DGRAD;
-  // three stages for the 32-wide tiles when every segment's halo fits 512 pixels (CVL_DISPATCH=h_no_3stage: two)
-  bool stg3 = !cvl_dispatch_flag("h_no_3stage");
-  for (int i = 0; stg3 && i < a.nseg; ++i) {
-    const HGeo g = h_geo(a.seg[i].Hr, a.seg[i].Wr);
-    if (g.rows * g.pitch > 512) stg3 = false;
-  }
-  if (a.Npad == 32) {          // 256 x 32 tiles (the FCOS heads' forward): persistent, no split, fp32 epilogue
-    if (a.stats || a.bsum) return -1;
-    static const int ncu32 = cvl_device_cus();
-    const int t32 = a.m_tiles;
-    a.splits = 1;
-    g_cvl_conv_last_kernel = CVL_CK_H64;
-    const dim3 gh(t32 < ncu32 ? t32 : ncu32);
-    if (stg3) hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, false, false, 32, 3>), gh, dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, false, false, 32>), gh, dim3(NT), 0, s, a);
-    return cvl_launch_status();
-  }
-  // 32-wide tiles (round 6) for the SW-epilogue launches whose 64-wide grid fills at most half of the
-  // CUs (the conv5_x 3x3 units at 512 / bs 16, forward and data gradient: 128 tiles -> 256): every CU
-  // gets a tile and no launch splits its channel blocks into fp32 slabs
-  {
-    static const int ncu0 = cvl_device_cus();
-    const int t64 = a.m_tiles * (a.Npad / BN);
-    bool n32 = !cvl_dispatch_flag("h_no_n32") && a.Npad % BN == 0 && 2 * t64 <= ncu0 && !d->dst_f32 &&
-               d->beta == 0.f && d->n_store % 8 == 0 && d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && !(a.stats && a.bsum);
-    for (int i = 0; n32 && i < a.nseg; ++i) {
-      const ConvSeg& q = a.seg[i];
-      const long hw = (long)q.Hr * q.Wr;
-      if (hw % BM || (a.bsum && q.dst_img != hw)) n32 = false;
-    }
-    if (n32) {
-      a.splits = 1;
-      g_cvl_conv_last_kernel = CVL_CK_H64;
-      const dim3 g32(2 * t64);
-      if (stg3 && d->mode == CVL_CONV_DGRAD && a.bsum)
-        hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, false, false, true, 32, 3>), g32, dim3(NT), 0, s, a);
-      else if (stg3 && d->mode == CVL_CONV_DGRAD)
-        hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, false, false, true, 32, 3>), g32, dim3(NT), 0, s, a);
-      else if (stg3)
-        hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, false, true, 32, 3>), g32, dim3(NT), 0, s, a);
-      else if (d->mode == CVL_CONV_DGRAD && a.bsum)
-        hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, false, false, true, 32>), g32, dim3(NT), 0, s, a);
-      else if (d->mode == CVL_CONV_DGRAD)
-        hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, false, false, true, 32>), g32, dim3(NT), 0, s, a);
-      else
-        hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, false, true, 32>), g32, dim3(NT), 0, s, a);
-      return cvl_launch_status();
-    }
-  }
-  const int tiles = a.m_tiles * (a.Npad / BN);
-  const int ncb = a.Cin / BK;
-  // split the channel blocks of grids that leave CUs idle (fp32 slabs, single segment, no fused
-  // BN-backward sums: the finish kernel forms BN statistics but not those)
-  int splits = 1;
-  const int target = cvl_tune_int("CVL_CONV_H_SPLIT_TARGET", 256);
-  if (tiles < target && a.nseg == 1 && !a.bsum && slab && d->n_store % 8 == 0 && d->dst_coff % 8 == 0 &&
-      (d->dst_f32 || d->ld_dst % 8 == 0) && d->n_store / 8 <= 256) {
-    splits = (target + tiles - 1) / tiles;
-    if (splits > ncb / 2) splits = ncb / 2;
-    if (splits < 1) splits = 1;
-    if ((size_t)splits * a.m_total * a.Npad * sizeof(float) > slab_bytes) splits = 1;
-  }
-  if (splits > 1) {
-    a.ksteps_per_split = (ncb + splits - 1) / splits;
-    a.splits = (ncb + a.ksteps_per_split - 1) / a.ksteps_per_split;
-    a.slab = reinterpret_cast<float*>(slab);
-  } else {
-    a.splits = 1;
-  }
-  // persistent: one workgroup per CU walks a contiguous chunk of tiles (split launches: one tile
-  // per workgroup, the K splits on blockIdx.z)
-  static const int ncu = cvl_device_cus();
-  const int per_cu = cvl_tune_int("CVL_CONV_H_WG_PER_CU", 1);
-  const int wgs = a.splits > 1 ? tiles : (tiles < ncu * per_cu ? tiles : ncu * per_cu);
-  dim3 grid(wgs, 1, a.splits);
-  g_cvl_conv_last_kernel = CVL_CK_H64;
-  const bool wres = a.splits <= 1 && a.Npad == BN && ncb <= WRES_CB && a.nseg == 1 && !cvl_dispatch_flag("h_no_wres");
-  // SW epilogue (registers -> 16-B stores, statistics per (image, N tile)): every tile inside one
-  // image, bf16 destination in 8-channel chunks, no beta, statistics OR fused BN sums
-  bool sw = a.splits <= 1 && !d->dst_f32 && d->beta == 0.f && d->n_store % 8 == 0 && d->ld_dst % 8 == 0 &&
-            d->dst_coff % 8 == 0 && !(a.stats && a.bsum) && !cvl_dispatch_flag("h_no_sw");
-  for (int i = 0; sw && i < a.nseg; ++i) {
-    const ConvSeg& q = a.seg[i];
-    const long hw = (long)q.Hr * q.Wr;
-    if (hw % BM || (a.bsum && q.dst_img != hw)) sw = false;
-  }
-  const bool bs = dg && a.bsum;
-#define CVL_H_LAUNCH(ST_)                                                                                             \
-  do {                                                                                                               \
-    if (sw) {                                                                                                        \
-      if (wres && !dg) hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, true, ST_, true>), grid, dim3(NT), 0, s, a); \
-      else if (wres && bs) hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, true, ST_, true>), grid, dim3(NT), 0, s, a); \
-      else if (wres) hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, true, ST_, true>), grid, dim3(NT), 0, s, a);    \
-      else if (bs) hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, false, ST_, true>), grid, dim3(NT), 0, s, a);      \
-      else if (dg) hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, false, ST_, true>), grid, dim3(NT), 0, s, a);     \
-      else hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, ST_, true>), grid, dim3(NT), 0, s, a);            \
-    } else {                                                                                                         \
-      if (wres && !dg) hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, true, ST_>), grid, dim3(NT), 0, s, a);       \
-      else if (wres && bs) hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, true, ST_>), grid, dim3(NT), 0, s, a);     \
-      else if (wres) hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, true, ST_>), grid, dim3(NT), 0, s, a);          \
-      else if (bs) hipLaunchKernelGGL((conv_igemm_h_kernel<true, true, false, ST_>), grid, dim3(NT), 0, s, a);            \
-      else if (dg) hipLaunchKernelGGL((conv_igemm_h_kernel<true, false, false, ST_>), grid, dim3(NT), 0, s, a);           \
-      else hipLaunchKernelGGL((conv_igemm_h_kernel<false, false, false, ST_>), grid, dim3(NT), 0, s, a);                  \
-    }                                                                                                                \
-  } while (0)
+// Launches H64 as planned (conv_dispatch.hip: plan_h chooses tile width, stages, split and epilogue).
+// A split launch leaves fp32 slabs for the caller's split-K finish.
+int launch_h(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
 #ifdef CVL_MEASURE
-  static const bool stamps = cvl_tune_flag("CVL_H_STAMPS");
-  if (stamps && a.splits <= 1 && wgs <= kHStampWgs) {
-    g_h_stamp_grid = wgs;
-    CVL_H_LAUNCH(true);
+  if (p.stamps) {
+    g_h_stamp_grid = p.grid;
+    h_launch<true>(p, a, s);
   } else
 #endif
   {
-    CVL_H_LAUNCH(false);
+    h_launch<false>(p, a, s);
   }
-#undef CVL_H_LAUNCH
-  int st = cvl_launch_status();
-  if (st || a.splits <= 1) return st;
-  return cvl_conv_splitk_finish(a, s);
-}
-
-// split-K workspace H64 would use for this descriptor (0: none)
-size_t cvl_conv_h_workspace(const cvl_conv_desc* d, const ConvArgs& a) {
-  if (!cvl_conv_h_fits(d, a) || a.nseg != 1 || a.Npad % BN) return 0;
-  const int tiles = a.m_tiles * (a.Npad / BN);
-  const int target = cvl_tune_int("CVL_CONV_H_SPLIT_TARGET", 256);
-  if (tiles >= target) return 0;
-  int splits = (target + tiles - 1) / tiles;
-  if (splits > (a.Cin / BK) / 2) splits = (a.Cin / BK) / 2;
-  return splits > 1 ? (size_t)splits * a.m_total * a.Npad * sizeof(float) : 0;
+  return cvl_launch_status();
 }

@@ -217,170 +217,34 @@ __global__ void __launch_bounds__(NT) conv_igemm_l_kernel(ConvArgs a) {
                                               BN <= 128 ? bcol : nullptr);
 }
 
+// The variants of one tile shape.  (Plain `if`s: the 256-wide SW and fused-sums forms are never
+// planned, but stay instantiated as they always were.)
+template <int BN_, int WGM_, int NST_>
+void l_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid);
+  if (p.sw && BN_ <= 128) {
+    with_bool(p.dgrad, [&](auto DG) {
+      hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, decltype(DG)::value, true, false, true>), grid, dim3(NT),
+                         0, s, a);
+    });
+  } else if (p.dgrad && p.bsum) {
+    hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, true, true, true>), grid, dim3(NT), 0, s, a);
+  } else {
+    with_bool(p.dgrad, [&](auto DG) {
+      with_bool(p.prio, [&](auto PRIO) {
+        hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, decltype(DG)::value, decltype(PRIO)::value>), grid,
+                           dim3(NT), 0, s, a);
+      });
+    });
+  }
+}
+
 }  // namespace
 
-int cvl_conv_igemm_x(const cvl_conv_desc* d, const ConvArgs& a, hipStream_t s);
-int cvl_conv_igemm_h(const cvl_conv_desc* d, const ConvArgs& a, hipStream_t s, void* slab, size_t slab_bytes);
-int cvl_conv_igemm_p(const cvl_conv_desc* d, const ConvArgs& a, hipStream_t s);
-
-// Called by cvl_conv_igemm when the launch qualifies (see cvl_conv_igemm_l_ok); returns -1 when
-// it does not, so the caller falls back to the 128-row kernel.
-int cvl_conv_igemm_l(const cvl_conv_desc* d, int dst_up, int dst_w, const void* src, void* dst, acc_u64* bn_stats,
-                     hipStream_t s, const BnSumArgs* bsum, void* workspace, size_t workspace_bytes) {
-  if (cvl_dispatch_flag("no_l")) return -1;
-  if (bsum && (d->mode != CVL_CONV_DGRAD || d->dst_f32 || (d->beta != 0.f && !bsum->y) || dst_up != 1 || bn_stats))
-    return -1;
-  // the residual (y-mask) form exists on the 1x1 persistent kernel only
-  if (bsum && bsum->y && (d->KH != 1 || d->KW != 1)) return -1;
-  // 3x3 / stride 1 forwards 32 wide into fp32 (the FCOS heads, 256 -> 20 / 5 over the five levels,
-  // fcos.py:85-88, 99-101): the halo kernel with 256 x 32 tiles -- one halo stage per 32-channel
-  // block feeds all nine taps, where the 128-row generic kernel re-gathers nine im2col tiles
-  if (d->Npad == 32 && d->KH == 3 && d->KW == 3 && d->mode == CVL_CONV_FWD && d->dst_f32 && !bn_stats &&
-      !bsum && dst_up == 1 && d->Cin % 32 == 0 && !d->relu_in && !cvl_dispatch_flag("no_h32")) {
-    ConvArgs ah;
-    if (cvl_conv_prepare(d, BM, &ah)) return -1;
-    ah.src = reinterpret_cast<const cvl_bf16*>(src);
-    ah.dst = dst;
-    ah.stats = nullptr;
-    return cvl_conv_igemm_h(d, ah, s, nullptr, 0);
-  }
-  // fp32 destinations store element-wise: any n_store (the RetinaNet box heads: 9 anchors x 4 = 36)
-  const bool n_ok = d->dst_f32 ? (d->n_store % 4 == 0 && !cvl_tune_flag("CVL_CONV_L_F32_N8")) : d->n_store % 8 == 0;
-  if (d->Cin % 32 != 0 || d->relu_in || !n_ok || (d->dst_f32 && bn_stats) ||
-      (!d->dst_f32 && (d->ld_dst % 8 || d->dst_coff % 8)) || (d->dst_f32 && cvl_tune_flag("CVL_CONV_L_NO_F32")))
-    return -1;
-  const bool l_cin = d->Cin % 64 == 0;          // the L / X kernels: 64-channel K steps
-  // 256-wide tiles (forward and data-gradient) for launches with >= CVL_CONV_L256_MIN_TILES of
-  // them.  A single FCOS tower's dgrad (341 tiles) lost 35 % on them (tools/conv_ab.py); the
-  // paired cls+reg tower dgrad (682 tiles) gains: whole step 813 -> 827 img/s
-  // (tools/gpu_knob_sweep.sh).  CVL_CONV_NO_DGRAD_256=1 restores forward-only.
-  const bool w256 = d->Npad % 256 == 0 && !cvl_dispatch_flag("no_256") &&
-                    (d->mode == CVL_CONV_FWD || !cvl_tune_flag("CVL_CONV_NO_DGRAD_256"));
-  const int bn = w256 ? 256 : (d->Npad % 128 == 0 ? 128 : (d->Npad % 64 == 0 ? 64 : 0));
-  if (!bn) return -1;
-  if (l_cin && d->KH * d->KW * d->Cin < cvl_tune_int("CVL_CONV_L_MIN_K", 0) && !bsum) return -1;   // A/B knob
-  ConvArgs a;
-  if (cvl_conv_prepare(d, BM, &a)) return -1;
-  a.dst_up = dst_up;
-  a.dst_w = dst_w;
-  // below 128 tiles the 128-row kernel with split-K fills the 256 CUs better (tests lower the
-  // bar).  Whole-step sweep (tools/gpu_knob_sweep.sh, FCOS bs=16): 384 -> 773, 256 -> 785,
-  // 192 -> 785, 128 -> 807, 1 -> 789 img/s (conv4_x 3x3 sits at exactly 128 tiles).  A launch
-  // with too few 256-wide tiles drops to the 128-wide tile first (since the X32 kernel: 256 tiles,
-  // e.g. one tower's 341-tile data gradient into F, FCOS 989 -> 995 img/s; 128: within noise).
-  // 1x1 launches: the persistent streaming kernel (conv_igemm_p.hip)
-  if (d->KH == 1 && d->KW == 1) {
-    ConvArgs ap = a;
-    ap.src = reinterpret_cast<const cvl_bf16*>(src);
-    ap.dst = dst;
-    ap.stats = bn_stats;
-    if (bsum) {
-      ap.bz = bsum->z; ap.bmr = bsum->mr; ap.bga = bsum->gamma; ap.bbe = bsum->beta; ap.bsum = bsum->sums;
-      ap.bhi = bsum->hi;
-      ap.by = bsum->y;
-    }
-    const int pst = cvl_conv_igemm_p(d, ap, s);
-    if (pst >= 0) return pst;
-    if (bsum && bsum->y) return -1;
-  }
-  const long min_tiles = cvl_dispatch_int("l_min_tiles", 128);
-  int use_bn = bn;
-  if (use_bn == 256 && (long)a.m_tiles * (a.Npad / 256) < cvl_dispatch_int("l256_min_tiles", 256)) use_bn = 128;
-  // short-K launches are HBM-bound: 128-wide tiles (more of them) beat the 256-wide ones (FCOS +0.6 %,
-  // CenterNet +0.4 % at K < 512)
-  const int w256_min_k = cvl_dispatch_int("w256_min_k", 512);
-  if (use_bn == 256 && a.K < w256_min_k) use_bn = 128;
-  // a launch that would leave CUs idle with 128-wide tiles takes 64-wide ones (twice the tiles),
-  // also when that lifts it over min_tiles (from the split-K 128-row kernel): FCOS A/B 970 -> 983
-  // img/s at 256 for the 128-tile conv4_x launches, -> 988 with the conv5_x ones (512: 966, 1024: 941)
-  const int fill = cvl_tune_int("CVL_CONV_L64_FILL", 256);
-  const bool fill_pre = !cvl_tune_flag("CVL_CONV_L64_NO_FILL_PRE");
-  const bool to64 = fill && use_bn == 128 && (long)a.m_tiles * (a.Npad / 128) < fill && a.Npad % 64 == 0 &&
-                    !(bsum && cvl_tune_flag("CVL_BSUM_NO_FILL"));
-  // 3x3 / stride 1 launches that would run 64-wide tiles: the halo-staged 256 x 64 kernel
-  // (conv_igemm_h.hip), whose A traffic is one halo per channel block instead of nine im2col tiles.
-  // Not where the 256 x 128 tiles fill the chip: there the L kernel reads each A tile once for 128
-  // columns (128 -> 128 @ 64^2, bs 16: L 33 / 47 us fwd / dgrad vs H64 41 / 52 us)
-  // 32-channel sources into 256-wide outputs (the FCOS heads' data gradient, K = 9 x 32): the X32
-  // ring kernel reads 64-B rows, i.e. one 32-channel block per K-tile (head dgrad 44.2 -> 30.7 us
-  // per head vs the H64 halo kernel; step +0.25 %)
-  if (!l_cin && d->Cin == 32 && bn == 256 && !bsum && !bn_stats && cvl_dispatch_int("x_cin32", 1)) {
-    ConvArgs ax = a;
-    ax.src = reinterpret_cast<const cvl_bf16*>(src);
-    ax.dst = dst;
-    ax.stats = nullptr;
-    const int xst = cvl_conv_igemm_x(d, ax, s);
-    if (xst >= 0) return xst;
-  }
-  const bool h_width = use_bn == 64 || to64 || !l_cin || cvl_tune_flag("CVL_CONV_H_ANY_N");
-  if (h_width && use_bn != 256 && (!bsum || ((a.seg[0].Hr * a.seg[0].Wr) % BM == 0 && !bn_stats))) {
-    ConvArgs ah = a;
-    ah.dst_up = dst_up;
-    ah.dst_w = dst_w;
-    ah.src = reinterpret_cast<const cvl_bf16*>(src);
-    ah.dst = dst;
-    ah.stats = bn_stats;
-    bool bs_ok = true;
-    if (bsum) {
-      for (int i = 0; i < ah.nseg; ++i)
-        if ((ah.seg[i].Hr * ah.seg[i].Wr) % BM || ah.seg[i].dst_img != (long)ah.seg[i].Hr * ah.seg[i].Wr) bs_ok = false;
-      ah.bz = bsum->z; ah.bmr = bsum->mr; ah.bga = bsum->gamma; ah.bbe = bsum->beta; ah.bsum = bsum->sums;
-      ah.bhi = bsum->hi;
-    }
-    if (bs_ok) {
-      const int hst = cvl_conv_igemm_h(d, ah, s, workspace, workspace_bytes);
-      if (hst >= 0) return hst;
-    }
-  }
-  if (!l_cin) return -1;
-  if (fill_pre && to64) use_bn = 64;
-  if ((long)a.m_tiles * (a.Npad / use_bn) < min_tiles) return -1;
-  if (to64) use_bn = 64;
-  if (bn_stats)
-    for (int i = 0; i < a.nseg; ++i)
-      if ((a.seg[i].Hr * a.seg[i].Wr) % 4) return -1;
-  if (bsum) {          // one image per 256-row tile; the 256-wide tiles keep their own epilogue budget
-    if (use_bn == 256) return -1;
-    for (int i = 0; i < a.nseg; ++i)
-      if ((a.seg[i].Hr * a.seg[i].Wr) % BM || a.seg[i].dst_img != (long)a.seg[i].Hr * a.seg[i].Wr) return -1;
-    a.bz = bsum->z; a.bmr = bsum->mr; a.bga = bsum->gamma; a.bbe = bsum->beta; a.bsum = bsum->sums;
-    a.bhi = bsum->hi;
-  }
-  a.src = reinterpret_cast<const cvl_bf16*>(src);
-  a.dst = dst;
-  a.stats = bn_stats;
-  dim3 grid(a.m_tiles * (a.Npad / use_bn));
-  const bool dg = d->mode == CVL_CONV_DGRAD;
-  const bool prio = !cvl_tune_flag("CVL_CONV_NO_PRIO");
-  // SW epilogue: bf16 destination in 8-channel chunks, no beta / scatter / fused sums; with BN
-  // statistics every tile inside one image
-  bool sw = !a.dst_f32 && a.beta == 0.f && !a.bsum && a.dst_up == 1 && a.n_store % 8 == 0 && a.ld_dst % 8 == 0 &&
-            a.dst_coff % 8 == 0 && !cvl_dispatch_flag("l_no_sw");
-  for (int i = 0; sw && a.stats && i < a.nseg; ++i)
-    if ((a.seg[i].Hr * a.seg[i].Wr) % BM) sw = false;
-#define CVL_L_LAUNCH(BN_, WGM_, NST_)                                                                          \
-  do {                                                                                                         \
-    if (sw && BN_ <= 128) {                                                                                     \
-      if (dg) hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, true, true, false, true>), grid, dim3(NT), 0, s, a); \
-      else hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, false, true, false, true>), grid, dim3(NT), 0, s, a);  \
-    } else if (dg && a.bsum) {                                                                                 \
-      hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, true, true, true>), grid, dim3(NT), 0, s, a);     \
-    } else if (dg) {                                                                                           \
-      if (prio) hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, true, true>), grid, dim3(NT), 0, s, a);   \
-      else hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, true, false>), grid, dim3(NT), 0, s, a);       \
-    } else {                                                                                                   \
-      if (prio) hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, false, true>), grid, dim3(NT), 0, s, a);  \
-      else hipLaunchKernelGGL((conv_igemm_l_kernel<BN_, WGM_, NST_, false, false>), grid, dim3(NT), 0, s, a);      \
-    }                                                                                                          \
-  } while (0)
-  if (use_bn == 256) {                    // the 8-phase 256 x 256 kernel when it applies
-    const int xst = cvl_conv_igemm_x(d, a, s);
-    if (xst >= 0) return xst;
-  }
-  g_cvl_conv_last_kernel = use_bn == 256 ? CVL_CK_L256 : (use_bn == 128 ? CVL_CK_L128 : CVL_CK_L64);
-  if (use_bn == 256) CVL_L_LAUNCH(256, 2, 2);
-  else if (use_bn == 128) CVL_L_LAUNCH(128, 4, 3);
-  else CVL_L_LAUNCH(64, 4, 3);
-#undef CVL_L_LAUNCH
+// Launches the L kernel the plan names (CVL_CK_L256 / L128 / L64).
+int launch_l(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.bn == 256) l_launch<256, 2, 2>(p, a, s);
+  else if (p.bn == 128) l_launch<128, 4, 3>(p, a, s);
+  else l_launch<64, 4, 3>(p, a, s);
   return cvl_launch_status();
 }

@@ -536,74 +536,38 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
   if (stamp) { stamp[1] = wall_clock64(); stamp[2] = total; }
 }
 
-}  // namespace
-
-// Runs a 1x1 launch on the persistent kernel; -1 when it does not apply.
-int cvl_conv_igemm_p(const cvl_conv_desc* d, const ConvArgs& a0, hipStream_t s) {
-  if (cvl_dispatch_flag("no_p")) return -1;
-  if (d->KH != 1 || d->KW != 1 || d->pad_t || d->pad_l || a0.relu_in || a0.nseg != 1 || a0.K % 32) return -1;
-  // bsum forms: z-mask without beta; y-mask (residual unit) with the beta accumulate
-  // (the residual form also on the strided data gradient's scatter, dst_up 2: the gap pixels' dy is 0,
-  // so the scattered rows' sums are the map's)
-  if (a0.bsum && ((d->mode != CVL_CONV_DGRAD && a0.dst_up == 1) || a0.dst_f32 || (a0.beta != 0.f) != (a0.by != nullptr) ||
-                  (a0.dst_up != 1 && !a0.by) || a0.stats || (a0.seg[0].Hr * a0.seg[0].Wr) % BM ||
-                  (a0.dst_up == 1 && a0.seg[0].dst_img != (long)a0.seg[0].Hr * a0.seg[0].Wr) ||
-                  a0.Npad % 64 || cvl_tune_flag("CVL_CONV_P_NO_BSUM")))
-    return -1;
-  if (d->mode == CVL_CONV_DGRAD && d->stride != 1) return -1;
-  const ConvSeg& q = a0.seg[0];
-  if (d->stride == 1 && (q.Hs != q.Hr || q.Ws != q.Wr)) return -1;
-  if (a0.dst_f32 ? (a0.n_store % 4 || a0.ld_dst % 4 || a0.dst_coff % 4)
-                 : (a0.n_store % 8 || a0.ld_dst % 8 || a0.dst_coff % 8))
-    return -1;
-  if (a0.stats && (a0.dst_f32 || (q.Hr * q.Wr) % BM)) return -1;
-  const long src_bytes = (q.src_base + (long)a0.B * q.src_img) * a0.Cin * 2;
-  if (src_bytes >= (long)kRecords - 65536 || (long)a0.Npad * a0.K * 2 >= (long)kRecords) return -1;
-  // N tile: 128 for short K (<= 256: fwd 1x1 64->256 @ 128^2 44 -> 36 us, 128->512 @ 64^2 31 -> 26,
-  // 256->1024 @ 32^2 25 -> 21), 64 for long K (1024->256 @ 32^2 20.5 vs 23, 2048->512 @ 16^2 29.5
-  // vs 35; tools/p_probe.py)
-  // ... and 128 where the output is much wider than K (512->2048 @ 16^2 fwd 22.4 -> 18.9 us; the
-  // same GEMM shape as conv5_x's 2048->512 data gradient), 64 for the long-K narrow ones
-  const bool wide = a0.K <= 256 || (a0.Npad >= 2 * a0.K && cvl_dispatch_int("p_wide128", 1));
-  const int bn = wide && a0.Npad % 128 == 0 ? 128 : (a0.Npad % 64 == 0 ? 64 : 0);
-  const int fbn = cvl_dispatch_int("p_bn", 0);
-  const int use = a0.bsum ? 64 : (fbn && a0.Npad % fbn == 0 ? fbn : bn);
-  if (!use) return -1;
-  const int ntiles = a0.m_tiles * (a0.Npad / use);
-  const int ntn = a0.Npad / use;
-  int grid = cvl_tune_int("CVL_CONV_P_WGS", 256);
-  if (grid >= ntiles) grid = ntiles;
-  else grid -= grid % ntn;                      // every workgroup keeps one N tile
-  if (grid < 1) return -1;
-  ConvArgs a = a0;
-  a.dbg = cvl_tune_int("CVL_P_ABLATE", 0);
-  // 64-deep K-tiles (128-B operand rows) wherever K allows; the 256-wide tile's ring has no room
-  const bool k64 = a.K % 64 == 0 && use != 256 && cvl_dispatch_int("p_k64", 1);
-  g_cvl_conv_last_kernel = CVL_CK_P;
-  g_cvl_conv_last_ktile = k64 ? 64 : 32;
-#define CVL_P_LAUNCH(BN_, BK_, ACC_)                                                                                 \
-  do {                                                                                                      \
-    if (a.bsum && a.by) {                                                                                   \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 2, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
-    } else if (a.bsum) {                                                                                    \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 1>), dim3(grid), dim3(NT), 0, s, a, ntiles);         \
-    } else if (a.dst_f32) {                                                                                 \
-      if (a.relu_out) hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
-      else hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, true>), dim3(grid), dim3(NT), 0, s, a, ntiles);            \
-    } else if (a.relu_out) {                                                                                \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                 \
-    } else if (a.beta != 0.f && !cvl_tune_flag("CVL_P_NO_ACC")) {                                            \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false, false, ACC_>), dim3(grid), dim3(NT), 0, s, a, ntiles);   \
-    } else {                                                                                                \
-      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false>), dim3(grid), dim3(NT), 0, s, a, ntiles);                \
-    }                                                                                                       \
-  } while (0)
-  if (use == 256) CVL_P_LAUNCH(256, 32, false);       // (the 256-wide ACC form spills)
-  else if (use == 128 && k64) CVL_P_LAUNCH(128, 64, true);
-  else if (use == 128) CVL_P_LAUNCH(128, 32, true);
-  else if (k64) CVL_P_LAUNCH(64, 64, true);
-  else CVL_P_LAUNCH(64, 32, true);
-#undef CVL_P_LAUNCH
-  return cvl_launch_status();
+// The epilogue forms of one tile shape.  The fused BN-sums forms exist 64 wide only (the plan gives
+// them bn 64); ACC_: whether this tile shape has the beta-accumulate form.
+template <int BN_, int BK_, bool ACC_>
+void p_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid);
+  const int ntiles = a.m_tiles * (a.Npad / p.bn);
+  if (p.bsum == CVL_BSUM_Y) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 2, true>), grid, dim3(NT), 0, s, a, ntiles);
+  } else if (p.bsum) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 1>), grid, dim3(NT), 0, s, a, ntiles);
+  } else if (a.dst_f32) {
+    with_bool(a.relu_out != 0, [&](auto RELU) {
+      hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, decltype(RELU)::value, true>), grid, dim3(NT), 0, s, a, ntiles);
+    });
+  } else if (a.relu_out) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, false>), grid, dim3(NT), 0, s, a, ntiles);
+  } else if (p.acc) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false, false, ACC_>), grid, dim3(NT), 0, s, a, ntiles);
+  } else {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false>), grid, dim3(NT), 0, s, a, ntiles);
+  }
 }
 
+}  // namespace
+
+// Launches the persistent 1x1 kernel as planned (conv_dispatch.hip: p_fits / plan_p say when it
+// applies and choose the tile).
+int launch_p(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.bn == 256) p_launch<256, 32, false>(p, a, s);       // (the 256-wide ACC form spills)
+  else if (p.bn == 128 && p.bk == 64) p_launch<128, 64, true>(p, a, s);
+  else if (p.bn == 128) p_launch<128, 32, true>(p, a, s);
+  else if (p.bk == 64) p_launch<64, 64, true>(p, a, s);
+  else p_launch<64, 32, true>(p, a, s);
+  return cvl_launch_status();
+}

@@ -305,49 +305,19 @@ __global__ void __launch_bounds__(NT) conv_igemm_x32_kernel(ConvArgs a) {
 
 }  // namespace
 
-// Called by cvl_conv_igemm_l for launches it would run on the 256 x 256 L tile; returns -1 when
-// the X kernel does not apply (the caller then launches the L kernel).
-int cvl_conv_igemm_x(const cvl_conv_desc* d, const ConvArgs& a, hipStream_t s) {
-  if (cvl_dispatch_flag("no_x")) return -1;
-  const bool dg = d->mode == CVL_CONV_DGRAD;
-  if (a.Npad % BN || a.Cin % BK32 || a.K / BK32 < 1 || d->KH * d->KW > 32 || a.relu_in ||
-      (dg && d->stride != 1) || a.dst_up != 1)
-    return -1;
-  // every source / weight byte offset must stay below the buffer-resource bound
-  for (int i = 0; i < a.nseg; ++i) {
-    const ConvSeg& q = a.seg[i];
-    const long src_bytes = (q.src_base + (long)a.B * q.src_img) * a.Cin * 2;
-    if (src_bytes >= (long)kRecords - 65536 || (long)a.Npad * a.K * 2 >= (long)kRecords) return -1;
-  }
-  dim3 grid(a.m_tiles * (a.Npad / BN));
-  ConvArgs am = a;
-  am.dbg = cvl_tune_int("CVL_X_ABLATE", 0);     // measurement builds (tools/x32_*.py): ablation bits
-  am.probe = reinterpret_cast<unsigned long long*>(cvl_probe_current(true));   // bench.py's in-step timing
-  g_cvl_conv_last_kernel = CVL_CK_X32;
-  g_cvl_conv_last_ktile = BK32;
-  // SW epilogue: bf16 destination in 8-channel chunks, no BN statistics, no beta
-  const bool sw = !a.dst_f32 && !a.stats && a.beta == 0.f && a.n_store % 8 == 0 && a.ld_dst % 8 == 0 &&
-                  a.dst_coff % 8 == 0 && !cvl_dispatch_flag("x_no_sw");
-  if (sw && g_cvl_ymask && !a.relu_out) {          // the ReLU mask in the register epilogue
-    am.ymask = reinterpret_cast<const cvl_bf16*>(g_cvl_ymask);
-    g_cvl_ymask_used = 1;
-  }
+// Launches X32 as planned (conv_dispatch.hip: x32_fits / plan_x say when it applies): data gradient
+// or forward, SW or C-image epilogue; a.ymask / a.probe ride in the arguments.
+int launch_x(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid);
+  with_bool(p.dgrad, [&](auto DG) {
+    with_bool(p.sw, [&](auto SW) {
 #ifdef CVL_MEASURE
-  if (am.dbg) {
-    if (dg && sw) hipLaunchKernelGGL((conv_igemm_x32_kernel<true, true, true>), grid, dim3(NT), 0, s, am);
-    else if (sw) hipLaunchKernelGGL((conv_igemm_x32_kernel<false, true, true>), grid, dim3(NT), 0, s, am);
-    else if (dg) hipLaunchKernelGGL((conv_igemm_x32_kernel<true, true>), grid, dim3(NT), 0, s, am);
-    else hipLaunchKernelGGL((conv_igemm_x32_kernel<false, true>), grid, dim3(NT), 0, s, am);
-  } else
+      if (p.dbg)
+        hipLaunchKernelGGL((conv_igemm_x32_kernel<decltype(DG)::value, true, decltype(SW)::value>), grid, dim3(NT), 0, s, a);
+      else
 #endif
-  if (sw && dg) {
-    hipLaunchKernelGGL((conv_igemm_x32_kernel<true, false, true>), grid, dim3(NT), 0, s, am);
-  } else if (sw) {
-    hipLaunchKernelGGL((conv_igemm_x32_kernel<false, false, true>), grid, dim3(NT), 0, s, am);
-  } else if (dg) {
-    hipLaunchKernelGGL((conv_igemm_x32_kernel<true>), grid, dim3(NT), 0, s, am);
-  } else {
-    hipLaunchKernelGGL((conv_igemm_x32_kernel<false>), grid, dim3(NT), 0, s, am);
-  }
+        hipLaunchKernelGGL((conv_igemm_x32_kernel<decltype(DG)::value, false, decltype(SW)::value>), grid, dim3(NT), 0, s, a);
+    });
+  });
   return cvl_launch_status();
 }

@@ -45,6 +45,7 @@ SIGNATURES = {
     "cvl_conv_igemm_relu_mask": (c_int, [P, P, P, P, P, c_size_t, P]),
     "cvl_conv_igemm_last_kernel": (c_int, []),
     "cvl_conv_igemm_last_ktile": (c_int, []),
+    "cvl_conv_igemm_plan": (c_int, [P, c_int, c_size_t, P, P]),
     "cvl_conv_kernel_name": (ctypes.c_char_p, [c_int]),
     "cvl_centernet_peak_decode_workspace_size": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "cvl_centernet_peak_decode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, P, P, P,
@@ -202,7 +203,7 @@ _lib = None
 
 
 # test / profiling queries that a CVL_LIB build of the parent revision (tools/build_base.sh) may lack
-NEWER = {"cvl_conv_igemm_last_ktile"}
+NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan"}
 
 
 def load():

@@ -201,6 +201,12 @@ int cvl_conv_igemm_last_kernel(void);
 /* K-tile depth (32 or 64 bf16) of the last launch of the tower kernel (CVL_CK_X32) or the persistent
  * 1x1 kernel (CVL_CK_P) on this host thread; 0 before the first one. */
 int cvl_conv_igemm_last_ktile(void);
+/* Test and profiling hook: the kernel family (*kernel, a CVL_CK_* code) and K-tile depth (*ktile, as
+ * cvl_conv_igemm_last_ktile reports it) that cvl_conv_igemm would use for d with these options
+ * (BN statistics requested or not; workspace_bytes 0 = no workspace).  Runs the launch planner only:
+ * host code, no device memory, no launch.  CVL_EINVAL where cvl_conv_igemm would reject d. */
+int cvl_conv_igemm_plan(const cvl_conv_desc* d, int with_bn_stats, size_t workspace_bytes, int32_t* kernel,
+                        int32_t* ktile);
 const char* cvl_conv_kernel_name(int code);
 
 /* Measurement hook (no reference counterpart: bench.py's in-step roofline timing).  cvl_probe_arm
