@@ -176,6 +176,11 @@ SIGNATURES = {
     "cvl_fcos_detect_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cvl_fcos_detect": (c_int, [P, c_int, P, c_int, c_int, P, P, c_int, c_int, c_float, c_float, c_int, c_int, P, P,
                                 P, P, P, c_size_t, P]),
+    # JPEG decode (include/cvlite.h "JPEG decode"; cvlite/jpeg.py)
+    "cvl_jpeg_info": (c_int, [P, c_size_t, P]),
+    "cvl_jpeg_entropy_decode": (c_int, [P, c_size_t, P, c_size_t, P]),
+    "cvl_jpeg_batch_sizes": (c_int, [P, c_int, P, P]),
+    "cvl_jpeg_decode_batch": (c_int, [P, P, c_int, P, P, c_size_t, P, c_size_t, P, P]),
     # fp32 parity mode (include/cvlite.h "fp32 parity mode")
     "cvl_bn_apply_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "cvl_bn_finalize_apply_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float,

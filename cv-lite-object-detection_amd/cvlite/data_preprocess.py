@@ -8,9 +8,10 @@
 
 The resize / normalise / pad (and the flip, when fused) run in one cvl_resize_pad_normalize
 launch per image that can write straight into a slot of the device batch.  JPEG decode
-(`_parse_image`, data_preprocess.py:5-9) is a host step (PIL's libjpeg; this ROCm image ships no
-rocJPEG / GPU JPEG decoder), as the reference's tf.image.decode_jpeg runs on the host CPU too;
-everything after it runs on the GPU.  The jitter draw uses numpy's generator instead of
+(`_parse_image`, data_preprocess.py:5-9) is by default a host step (PIL's libjpeg), as the
+reference's tf.image.decode_jpeg runs on the host CPU too; decode="gpu" takes cvlite.jpeg instead
+(host Huffman threads + HIP IDCT / upsampling / colour, the same pixels).  Everything after the
+decode runs on the GPU.  The jitter draw uses numpy's generator instead of
 tf.random.uniform (a different stream by construction).
 """
 import numpy as np
@@ -95,7 +96,7 @@ def box_targets(bbox, flip):
     return np.concatenate([(s[:, :2] + s[:, 2:]) / f32(2.0), s[:, 2:] - s[:, :2]], -1).astype(f32)
 
 
-def preprocess_data(sample, img_dims=384, pad_flag=True, rng=None, out=None):
+def preprocess_data(sample, img_dims=384, pad_flag=True, rng=None, out=None, decode="host"):
     """data_preprocess.py:98-133 preprocess_data(sample, img_dims, pad_flag) for one sample dict with
     the reference's keys: image (a file name, decoded on the host by _parse_image, or an already
     decoded [H,W,3] image, uint8 or fp32, host or device), objects = {bbox [N,4] normalised, label
@@ -105,12 +106,20 @@ def preprocess_data(sample, img_dims=384, pad_flag=True, rng=None, out=None):
     pad_flag=False: resize to [img_dims, img_dims] (:111-113), flip, /127.5 - 1 (:124-125),
     img_shp = [img_dims, img_dims] -- one fused launch either way, in the reference's order (pad_flag
     True: flip, then resize; False: resize, then flip its output).  The flip draw (p = 0.5) and the jitter draw use `rng`
-    (numpy) in the reference's order: flip first, then the jitter size."""
+    (numpy) in the reference's order: flip first, then the jitter size.
+    decode: how a file name is decoded -- "host" (_parse_image, PIL) or "gpu" (cvlite.jpeg.decode: the
+    same pixels, the IDCT / upsampling / colour conversion in HIP)."""
+    if decode not in ("host", "gpu"):
+        raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
     rng = rng if rng is not None else np.random.default_rng()
     jitter = [sample["l_jitter"], sample["u_jitter"]]
     image = sample["image"]
     if isinstance(image, str):                   # a file name, as the reference's samples hold
-        image = _parse_image(image)
+        if decode == "gpu":
+            from . import jpeg
+            image = jpeg.decode(image)
+        else:
+            image = _parse_image(image)
     flip = bool(rng.uniform() <= 0.5)
     if pad_flag:
         img, new_shape, _ = preprocess_image(image, jitter=jitter, min_side=sample["min_side"],

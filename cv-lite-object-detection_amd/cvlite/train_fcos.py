@@ -261,13 +261,23 @@ class JitterFCOSTrainer(object):
         return None if self.l2 is None else self.l2.out
 
 
-def _raw_batch(train_data, idx, rng):
+def _raw_batch(train_data, idx, rng, jpeg_decode="host"):
     """preprocess_data (data_preprocess.py:98-133) of each chosen raw sample: device images of their
-    own padded sizes + boxes / counts / unpadded sizes for the bucketed step."""
+    own padded sizes + boxes / counts / unpadded sizes for the bucketed step.  jpeg_decode="gpu":
+    the file-name samples of the batch are decoded first, in one cvlite.jpeg.decode_batch call, and
+    preprocess_data takes the decoded device images (the flip / jitter draws keep their order)."""
     from .data_preprocess import preprocess_data
+    if jpeg_decode not in ("host", "gpu"):
+        raise ValueError("jpeg_decode must be 'host' or 'gpu', not %r" % (jpeg_decode,))
+    samples = [train_data[i] for i in idx]
+    if jpeg_decode == "gpu":
+        from . import jpeg
+        named = [k for k, s in enumerate(samples) if isinstance(s["image"], str)]
+        for k, img in zip(named, jpeg.decode_batch([samples[k]["image"] for k in named])):
+            samples[k] = dict(samples[k], image=img)
     imgs, boxes, dims = [], [], []
-    for i in idx:
-        img, bbox, cls, shp = preprocess_data(train_data[i], rng=rng)
+    for sample in samples:
+        img, bbox, cls, shp = preprocess_data(sample, rng=rng)
         imgs.append(img)
         boxes.append(np.concatenate([bbox, cls.astype(np.float32)[:, None]], 1))
         dims.append(shp)
@@ -333,7 +343,7 @@ def _batch_from_samples(train_data, idx, n_max):
 def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_manager, st_step, max_steps,
           init_lr=1.0e-3, min_lr=1.0e-5, decay_step=1000, decay_rate=0.99, display_step=50, step_save=100,
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
-          max_decays=None):
+          max_decays=None, jpeg_decode="host"):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -358,6 +368,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       cvlite.train_centernet.Adam (Keras Adam, what train_fcos_center_voc.py:327 trains with);
       max_decays caps the decay exponent (the centre loops' step schedule, :150-157).  A string
       ckpt prefix saves the optimizer's slots too (SGD momentum or Adam m / v / iterations).
+    * jpeg_decode (cvlite extension): "host" decodes file-name samples with PIL one by one, "gpu"
+      decodes each batch's files in one cvlite.jpeg.decode_batch call (the same pixels).
     The reference's thermal "Cooling GPU" sleep runs only with CVL_COOLING=1.  Returns None."""
     from . import checkpoint as ck
     import torch.distributed as tdist
@@ -403,7 +415,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
             idx = t.cpu().numpy()
         idx = idx[rank * batch_size:(rank + 1) * batch_size]
         if raw:
-            imgs, bx, nb, dims = _raw_batch(train_data, idx, rng)
+            imgs, bx, nb, dims = _raw_batch(train_data, idx, rng, jpeg_decode)
             per_img = trainer.step(imgs, bx, nb, dims).detach().double()
         else:
             imgs, bx, nb, dims = _batch_from_samples(train_data, idx, n_max)

@@ -853,6 +853,58 @@ int cvl_image_augment(const float* img_src, float* img_dst, const float* tgt_src
                       const int32_t* ops, const float* params, int B, int N, int S, int T, void* workspace,
                       size_t workspace_bytes, cvl_stream_t stream);
 
+/* ==========================================================================================
+ * JPEG decode (FCOS/data_preprocess.py:5-9 `_parse_image`, tf.image.decode_jpeg): the file bytes
+ * -> [H][W][3] uint8 RGB, bit-identical to libjpeg's default decode (islow IDCT, fancy upsampling),
+ * i.e. to PIL's Image.open(...).convert("RGB").  Hybrid: the Huffman bit stream is decoded on the
+ * host (std::threads, several images at once), dequantise + inverse DCT + chroma upsampling +
+ * YCbCr->RGB + crop run on the GPU, two launches per batch.
+ *
+ * Supported files: baseline (SOF0) 8-bit, one interleaved scan of all components, greyscale or
+ * YCbCr with luma sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and 1x1 chroma, 8-bit
+ * quantisation tables, 1 <= width, height <= 8192, restart intervals allowed.  Everything else
+ * (progressive, arithmetic, 12-bit, CMYK / YCCK, RGB-coded, other samplings, several scans, not a
+ * JPEG) is CVL_JPEG_UNSUPPORTED; a truncated or inconsistent stream, or one libjpeg would only
+ * decode with warnings, is CVL_JPEG_CORRUPT.  Neither reads or writes out of range.
+ * ========================================================================================== */
+enum { CVL_JPEG_UNSUPPORTED = 2, CVL_JPEG_CORRUPT = 3 };
+#define CVL_JPEG_MAX_BATCH 4096
+
+/* Host only: parses the segments up to the scan.  data: HOST bytes of the file.  info: HOST int32
+ * [8] = {status, width, height, components (1 or 3), hmax, vmax (luma sampling), restart interval
+ * in MCUs (0 = none), coefficient count (int16 elements, blocks padded to whole MCUs)}; all but
+ * the status are 0 when the status (also the return value) is not CVL_OK. */
+int cvl_jpeg_info(const uint8_t* data, size_t nbytes, int32_t* info /*host[8]*/);
+
+/* Host only, no GPU call: the entropy decode of one file.  coef: HOST int16, the quantised (not
+ * dequantised) coefficients in natural (de-zigzagged) order, component-planar
+ * [comp][block_row][block_col][64]; coef_cap = its capacity in elements (CVL_EINVAL when below the
+ * coefficient count of cvl_jpeg_info).  qt: HOST uint16 [3][64], the quantisation table of each
+ * component in natural order (rows of absent components zero).  Returns CVL_OK or the file's
+ * status; coef / qt hold partial data after CVL_JPEG_CORRUPT. */
+int cvl_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coef, size_t coef_cap,
+                            uint16_t* qt /*host[3][64]*/);
+
+/* Host only: the buffer sizes of cvl_jpeg_decode_batch for n images whose coefficient counts
+ * (cvl_jpeg_info; 0 for an image that is not CVL_OK) are coef_counts (HOST). */
+int cvl_jpeg_batch_sizes(const int32_t* coef_counts, int n, size_t* staging_bytes, size_t* workspace_bytes);
+
+/* Decodes n files in one call.  data / nbytes: HOST arrays of n HOST byte pointers and lengths;
+ * out: HOST array of n DEVICE pointers, image i written as [H_i][W_i][3] uint8 (sizes from
+ * cvl_jpeg_info); staging: a PINNED HOST buffer and workspace a DEVICE buffer of at least the
+ * cvl_jpeg_batch_sizes bytes, both 16-byte aligned; status: HOST int32 [n], the status of each
+ * image.  The call entropy-decodes on min(n, CVL_JPEG_THREADS) threads (environment, default 8,
+ * clamped to 1..16) into staging, then enqueues on `stream` one copy of the used staging bytes into
+ * workspace and the two kernels over the whole batch (images of different sizes and samplings mix).
+ * An image whose status is not CVL_OK is skipped -- its output is untouched -- and the call still
+ * returns CVL_OK.  No allocation of device or pinned memory and no device synchronisation inside:
+ * staging and workspace are in use until the enqueued work has run, so the caller must not reuse
+ * them (another batch included) before that (record an event on `stream`, wait for it).  Unlike the
+ * kernels-only entries this one runs host work and a copy; it is not for capture into a hipGraph. */
+int cvl_jpeg_decode_batch(const uint8_t* const* data, const size_t* nbytes, int n, uint8_t* const* out,
+                          void* staging, size_t staging_bytes, void* workspace, size_t workspace_bytes,
+                          int32_t* status, cvl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
