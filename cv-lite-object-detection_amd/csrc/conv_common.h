@@ -90,6 +90,7 @@ struct ConvArgs {
   acc_u64* bsum;
   float bhi;
   const cvl_bf16* by;     // non-null: the ReLU mask comes from y > 0 (a residual unit's output), not bn(z)
+  const uint8_t* bbits;   // ... or from y's ReLU sign bitmap (uint8 [rows][ld_dst / 8], bit u = y[8c + u] > 0)
   unsigned long long* probe;   // cvl_probe_arm slot of this launch (kernels that support it), or null
   const cvl_bf16* ymask;       // data gradient through a ReLU: outputs where ymask <= 0 stored as 0 (X32 SW only)
 };
@@ -140,11 +141,13 @@ struct BnSumArgs {
   acc_u64* sums;
   float hi;
   const cvl_bf16* y;      // residual unit: mask y > 0 (null: rebuilt from z)
+  const uint8_t* bits;    // residual unit: y's ReLU sign bitmap (CVL_BSUM_BITS), laid out as y / 8
 };
 
 // ---- forward / data-gradient dispatch (conv_dispatch.hip) ---------------------------------------
 // What a call offers beyond its descriptor.
-enum { CVL_BSUM_NONE = 0, CVL_BSUM_Z = 1, CVL_BSUM_Y = 2 };   // fused BN-backward sums: mask from bn(z) / from y
+// fused BN-backward sums: mask from bn(z) / from y / from y's ReLU sign bitmap (planned as the y form)
+enum { CVL_BSUM_NONE = 0, CVL_BSUM_Z = 1, CVL_BSUM_Y = 2, CVL_BSUM_BITS = 3 };
 struct ConvCallOpts {
   bool bn_stats;            // BN statistics requested
   int bsum;                 // fused BN-backward sums offered (CVL_BSUM_*)
@@ -234,6 +237,7 @@ static inline int cvl_conv_prepare(const cvl_conv_desc* d, int bm, ConvArgs* a) 
   a->dbg = 0;
   a->bz = nullptr; a->bmr = nullptr; a->bga = nullptr; a->bbe = nullptr; a->bsum = nullptr; a->bhi = 0.f;
   a->by = nullptr;
+  a->bbits = nullptr;
   a->probe = nullptr;
   a->ymask = nullptr;
   a->acc_slots = cvl_bn_acc_slots();

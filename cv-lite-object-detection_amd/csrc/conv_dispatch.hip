@@ -177,7 +177,9 @@ bool p_fits(const cvl_conv_desc* d, const ConvArgs& a, const ConvCallOpts& o) {
   // bsum forms: z-mask without beta; y-mask (residual unit) with the beta accumulate
   // (the residual form also on the strided data gradient's scatter, dst_up 2: the gap pixels' dy is 0,
   // so the scattered rows' sums are the map's)
-  const bool by = o.bsum == CVL_BSUM_Y;
+  const bool by = o.bsum == CVL_BSUM_Y || o.bsum == CVL_BSUM_BITS;
+  // (the bitmap holds one byte per 8-channel chunk of a y row: whole chunks only)
+  if (o.bsum == CVL_BSUM_BITS && (a.ld_dst % 8 || a.dst_coff % 8)) return false;
   if (o.bsum && ((d->mode != CVL_CONV_DGRAD && a.dst_up == 1) || a.dst_f32 || (a.beta != 0.f) != by ||
                  (a.dst_up != 1 && !by) || o.bn_stats || (a.seg[0].Hr * a.seg[0].Wr) % BM ||
                  (a.dst_up == 1 && a.seg[0].dst_img != (long)a.seg[0].Hr * a.seg[0].Wr) || a.Npad % 64))
@@ -286,11 +288,15 @@ bool large_fits(const cvl_conv_desc* d, const ConvCallOpts& o) {
 // false: none of them takes the launch (the 128-row kernel does; a fused BN-sums offer is declined)
 bool plan_large(const cvl_conv_desc* d, const ConvArgs& a, const ConvCallOpts& o, ConvPlan* p) {
   if (cvl_dispatch_flag("no_l")) return false;
-  const bool bs = o.bsum != CVL_BSUM_NONE, by = o.bsum == CVL_BSUM_Y;
-  // (dst_up != 1 also turns away the residual form on a strided data gradient's scatter, which P's
-  // predicate provides for: as found, kept)
-  if (bs && (d->mode != CVL_CONV_DGRAD || d->dst_f32 || (d->beta != 0.f && !by) || a.dst_up != 1 || o.bn_stats))
+  const bool bs = o.bsum != CVL_BSUM_NONE, by = o.bsum == CVL_BSUM_Y || o.bsum == CVL_BSUM_BITS;
+  // the residual form on a strided 1x1 data gradient's scatter (the descriptor rewritten as the dense
+  // forward GEMM over the dY grid, dst_up 2): the persistent kernel only, whose predicate provides
+  // for it (offered by CVL_DISPATCH=bnsum_res_s2 only)
+  const bool scat = by && a.dst_up != 1 && d->KH == 1 && d->KW == 1 && d->mode == CVL_CONV_FWD;
+  if (bs && !scat &&
+      (d->mode != CVL_CONV_DGRAD || d->dst_f32 || (d->beta != 0.f && !by) || a.dst_up != 1 || o.bn_stats))
     return false;
+  if (scat && (d->dst_f32 || o.bn_stats)) return false;
   // the residual (y-mask) form exists on the 1x1 persistent kernel only
   if (by && (d->KH != 1 || d->KW != 1)) return false;
   // 3x3 / stride 1 forwards 32 wide into fp32 (the FCOS heads, 256 -> 20 / 5 over the five levels,

@@ -514,6 +514,7 @@ void fill_args(const ConvPlan& p, const ConvIo& io, ConvArgs* a) {
     const BnSumArgs& b = *io.bsum;
     a->bz = b.z; a->bmr = b.mr; a->bga = b.gamma; a->bbe = b.beta; a->bsum = b.sums; a->bhi = b.hi;
     a->by = b.y;
+    a->bbits = b.bits;
   }
   if (p.ymask) a->ymask = reinterpret_cast<const cvl_bf16*>(io.ymask);
   // bench.py's in-step timing: the tower kernel takes the call's armed slot
@@ -637,6 +638,20 @@ extern "C" int cvl_conv_igemm_relu_mask(const cvl_conv_desc* d, const void* src,
 }
 
 namespace {
+// The form a fused BN-sums offer ends up with: the offer itself, the y form where only the bitmap
+// form is declined, or CVL_BSUM_NONE.
+int dgrad_bnsum_plan_form(const cvl_conv_desc* d, int offer, size_t ws, int32_t* form) {
+  *form = CVL_BSUM_NONE;
+  if (d->prec == CVL_PREC_F32) return CVL_OK;
+  for (int f = offer; f != CVL_BSUM_NONE; f = f == CVL_BSUM_BITS ? CVL_BSUM_Y : CVL_BSUM_NONE) {
+    ConvPlan p;
+    const int st = conv_plan(d, ConvCallOpts{false, f, false, ws}, &p);
+    if (st) return st;
+    if (p.kernel != CVL_CK_NONE) { *form = f; break; }
+  }
+  return CVL_OK;
+}
+
 // The two fused BN-sums entries: plan with the sums offered; where no kernel can fuse them, plan
 // the plain data gradient (*fused = 0: the caller then runs the two-pass BN backward).
 int dgrad_bnsum_call(const cvl_conv_desc* d, const void* src, void* dst, int form, const BnSumArgs& b, int32_t* fused,
@@ -669,7 +684,7 @@ extern "C" int cvl_conv_igemm_dgrad_bnsum(const cvl_conv_desc* d, const void* sr
                                           cvl_stream_t stream) {
   CVL_CHECK_ARG(d && fused && z && mean_rstd && gamma && beta && sums);
   const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
-                    act_hi, nullptr};
+                    act_hi, nullptr, nullptr};
   return dgrad_bnsum_call(d, src, dst, CVL_BSUM_Z, b, fused, workspace, workspace_bytes, stream);
 }
 
@@ -683,6 +698,46 @@ extern "C" int cvl_conv_igemm_dgrad_bnsum_res(const cvl_conv_desc* d, const void
                                               size_t workspace_bytes, cvl_stream_t stream) {
   CVL_CHECK_ARG(d && fused && y && z && mean_rstd && gamma && beta && sums);
   const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
-                    INFINITY, reinterpret_cast<const cvl_bf16*>(y)};
+                    INFINITY, reinterpret_cast<const cvl_bf16*>(y), nullptr};
   return dgrad_bnsum_call(d, src, dst, CVL_BSUM_Y, b, fused, workspace, workspace_bytes, stream);
+}
+
+// The same with the mask read from y's ReLU sign bitmap (cvl_bn_finalize_apply_bits): one byte per
+// 8-channel chunk instead of the 16-byte y chunk.  Where the planner declines the bitmap form
+// (ld_dst / dst_coff not multiples of 8) the y form runs; *form (optional) reports which
+// (CVL_BSUM_BITS 3 / CVL_BSUM_Y 2; 0 when not fused).
+extern "C" int cvl_conv_igemm_dgrad_bnsum_res_bits(const cvl_conv_desc* d, const void* src, void* dst, const void* y,
+                                                   const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                                                   const float* gamma, const float* beta, uint64_t* sums,
+                                                   int32_t* fused, int32_t* form, void* workspace,
+                                                   size_t workspace_bytes, cvl_stream_t stream) {
+  CVL_CHECK_ARG(d && fused && y && relu_bits && z && mean_rstd && gamma && beta && sums);
+  const BnSumArgs b{reinterpret_cast<const cvl_bf16*>(z), mean_rstd, gamma, beta, reinterpret_cast<acc_u64*>(sums),
+                    INFINITY, reinterpret_cast<const cvl_bf16*>(y), relu_bits};
+  int32_t tmp = 0, *pf = form ? form : &tmp;
+  *pf = 0;
+  int st = dgrad_bnsum_plan_form(d, CVL_BSUM_BITS, workspace ? workspace_bytes : 0, pf);
+  if (st) return st;
+  st = dgrad_bnsum_call(d, src, dst, *pf ? *pf : CVL_BSUM_Y, b, fused, workspace, workspace_bytes, stream);
+  if (st || !*fused) *pf = 0;
+  return st;
+}
+
+// Test and profiling hook: the fused BN-sums form (*form: CVL_BSUM_* code, 0 = none, the plain data
+// gradient runs) and kernel family / K-tile a cvl_conv_igemm_dgrad_bnsum* call offering `offer` would
+// use (offer CVL_BSUM_BITS falls back to CVL_BSUM_Y as the entry does).  Host only, no launch.
+extern "C" int cvl_conv_igemm_plan_bnsum(const cvl_conv_desc* d, int offer, size_t workspace_bytes, int32_t* form,
+                                         int32_t* kernel, int32_t* ktile) {
+  CVL_CHECK_ARG(d && form && kernel && ktile && offer >= CVL_BSUM_Z && offer <= CVL_BSUM_BITS);
+  *form = 0;
+  *kernel = CVL_CK_NONE;
+  *ktile = 0;
+  if (d->prec == CVL_PREC_F32) return CVL_OK;
+  int st = dgrad_bnsum_plan_form(d, offer, workspace_bytes, form);
+  if (st) return st;
+  ConvPlan p;
+  if ((st = conv_plan(d, ConvCallOpts{false, *form, false, workspace_bytes}, &p))) return st;
+  *kernel = p.kernel;
+  *ktile = conv_plan_ktile(p);
+  return CVL_OK;
 }

@@ -99,6 +99,13 @@ __device__ __forceinline__ s16x8 gload16_untracked(const void* p) {
   return v;
 }
 __device__ __forceinline__ void pin16(s16x8& v) { asm volatile("" : "+v"(v)); }
+// one byte, zero-extended, the same way (the ReLU sign bitmap of the fused residual sums)
+__device__ __forceinline__ unsigned gload1_untracked(const void* p) {
+  unsigned v;
+  asm volatile("global_load_ubyte %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+__device__ __forceinline__ void pin1(unsigned& v) { asm volatile("" : "+v"(v)); }
 
 template <int BN, int BK, bool RELU, bool F32, int BS = 0, bool ACC = false>
 __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles) {
@@ -219,7 +226,8 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
       bcol[j][e] = (S.bias && n < a.n_store) ? S.bias[n] : 0.f;
     }
   // fused BN-backward sums (BS, data gradient; 1: ReLU mask rebuilt from z, 2: residual unit, mask
-  // y > 0 from its output y, sums over the FINAL value after the beta accumulate): the lane's 8
+  // y > 0 from its output y, sums over the FINAL value after the beta accumulate, 3: the same with
+  // the mask from y's ReLU sign bitmap, one byte per 8-channel chunk): the lane's 8
   // channels per column-block pair after
   // the store regrouping; gamma / beta now, (mean, rstd) per image in the epilogue
   constexpr int NJP = BS ? TN / 2 : 1;
@@ -241,6 +249,7 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
   wait_vm<0>();
   s16x8 zv[BS ? TM : 1][NJP];
   s16x8 yv[BS == 2 ? TM : 1][BS == 2 ? NJP : 1];
+  unsigned bv[BS == 3 ? TM : 1][BS == 3 ? NJP : 1];      // BS 3: the chunk's byte of y's ReLU sign bitmap
   // ACC (bf16 dst, beta != 0): the tile's old dst chunks, prefetched with its first K-tile like z (a
   // plain load in the epilogue made the compiler drain the DMA ring at every tile)
   s16x8 ov[ACC ? TM : 1][ACC ? TN / 2 : 1];
@@ -334,6 +343,7 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
         for (int jp = 0; jp < NJP; ++jp) {
           pin16(zv[i][jp]);
           if (BS == 2) pin16(yv[i][jp]);
+          if (BS == 3) pin1(bv[i][jp]);
         }
       const int img = m0 / HWr;
       if (img != bimg) {
@@ -431,6 +441,8 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
             bool on;
             if (BS == 2) {
               on = bf16_to_f32((cvl_bf16)yv[i][j / 2][u]) > 0.f;
+            } else if (BS == 3) {
+              on = (bv[i][j / 2] >> u) & 1u;
             } else {
               const float af = __builtin_fmaf(bga[j / 2][u], xh, bbe[j / 2][u]);
               on = af > 0.f && af < a.bhi;
@@ -508,6 +520,8 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
           zv[i][jp] = gload16_untracked(a.bz + row * a.ld_dst + a.dst_coff + n0 + wn * C::WN + jp * 32 + lgo);
           if (BS == 2)
             yv[i][jp] = gload16_untracked(a.by + row * a.ld_dst + a.dst_coff + n0 + wn * C::WN + jp * 32 + lgo);
+          if (BS == 3)       // (ld_dst, dst_coff and the chunk's column are multiples of 8: conv_dispatch.hip)
+            bv[i][jp] = gload1_untracked(a.bbits + ((row * a.ld_dst + a.dst_coff + n0 + wn * C::WN + jp * 32 + lgo) >> 3));
         }
     }
     const char* sl = lds + rslot * C::SLOT_B;
@@ -542,7 +556,9 @@ template <int BN_, int BK_, bool ACC_>
 void p_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
   const dim3 grid(p.grid);
   const int ntiles = a.m_tiles * (a.Npad / p.bn);
-  if (p.bsum == CVL_BSUM_Y) {
+  if (p.bsum == CVL_BSUM_BITS) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 3, true>), grid, dim3(NT), 0, s, a, ntiles);
+  } else if (p.bsum == CVL_BSUM_Y) {
     hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 2, true>), grid, dim3(NT), 0, s, a, ntiles);
   } else if (p.bsum) {
     hipLaunchKernelGGL((conv_igemm_p_kernel<64, BK_, false, false, 1>), grid, dim3(NT), 0, s, a, ntiles);

@@ -321,12 +321,13 @@ __device__ __forceinline__ void bn_fin_running(const BnFin& fin, int nimg, int C
       bn_running(fin.stats, fin.slots, nimg, C, c, HW, fin.eps, fin.momentum, fin.run_mean, fin.run_var);
 }
 
-template <bool FIN, bool RBN = false>
+// BITS: also write the ReLU sign bitmap of y (a compile-time form: the others keep their code)
+template <bool FIN, bool RBN = false, bool BITS = false>
 __global__ void __launch_bounds__(NT) bn_apply_kernel(const cvl_bf16* __restrict__ z, const float* __restrict__ mr,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const cvl_bf16* __restrict__ res, cvl_bf16* __restrict__ y,
                                                       int C, int HW, int relu, int rows_per_blk, BnFin fin,
-                                                      BnRes rb) {
+                                                      BnRes rb, uint8_t* __restrict__ bits) {
   static_assert(FIN || !RBN, "the BN residual form fuses both finalizes");
   const int b = FIN ? (int)blockIdx.y - 1 : (int)blockIdx.y;     // FIN: row 0 advances the running stats
   const int C8 = C / 8;
@@ -403,7 +404,16 @@ __global__ void __launch_bounds__(NT) bn_apply_kernel(const cvl_bf16* __restrict
           if (relu == 2) o = fminf(o, 6.0f);                     // ReLU6 (MobileNetV2)
           v[u] = o;
         }
-        *reinterpret_cast<s16x8*>(y + off[q]) = pack8(v);
+        const s16x8 pv = pack8(v);
+        *reinterpret_cast<s16x8*>(y + off[q]) = pv;
+        if (BITS) {                   // ReLU sign bitmap [B*HW][C/8]: bit u = stored (rounded) y[c0 + u] > 0
+          float rv[8];
+          unpack8(pv, rv);
+          unsigned mk = 0;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) mk |= (rv[u] > 0.f ? 1u : 0u) << u;
+          bits[off[q] >> 3] = (uint8_t)mk;
+        }
       }
     }
   }
@@ -468,7 +478,9 @@ struct BnPG {
 };
 
 // MASK selects the ReLU-mask source at compile time (1: y, 2: bn_affine(z) recomputed, 3: no mask --
-// BN without ReLU; 0: decided at run time from y / bnb) -- the run-time form holds the registers of both paths (pass 0: 215 VGPRs,
+// BN without ReLU; 4: the ReLU sign bitmap the forward wrote beside y, passed in y's place -- uint8
+// [B*HW][C/8], bit u of a byte = y[8-channel chunk][u] > 0, one byte per chunk instead of the 16-byte
+// y row; 0: decided at run time from y / bnb) -- the run-time form holds the registers of both paths (pass 0: 215 VGPRs,
 // 2 waves/SIMD; pass 1: 141, 3 waves), the specialised ones fit 4-5 waves
 template <int PASS, int MASK = 0, bool SC = false>
 __global__ void __launch_bounds__(NT) bn_bwd_kernel(const cvl_bf16* __restrict__ dy, const cvl_bf16* __restrict__ y,
@@ -522,6 +534,7 @@ __global__ void __launch_bounds__(NT) bn_bwd_kernel(const cvl_bf16* __restrict__
     // mask source: y (relu output, residual units) or, when y is null and bnb is given, the
     // ReLU of bn_affine(z) recomputed (non-residual units: one tensor fewer to read)
     const bool use_y = PASS != 2 && (MASK == 0 ? y != nullptr : MASK == 1);
+    constexpr bool use_b = PASS != 2 && MASK == 4;
     const bool zmask = PASS != 2 && (MASK == 0 ? (!y && bnb) : MASK == 2);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -545,6 +558,7 @@ __global__ void __launch_bounds__(NT) bn_bwd_kernel(const cvl_bf16* __restrict__
     if (rsub < rpp && act) {
       for (int r = r0 + rsub; r < r1; r += rpp * BN_UNR) {
         s16x8 vg[BN_UNR], vz[BN_UNR], vy[BN_UNR], vs[SC ? BN_UNR : 1];
+        unsigned vb[BN_UNR];
         long off[BN_UNR];
 #pragma unroll
         for (int q = 0; q < BN_UNR; ++q) {
@@ -553,6 +567,7 @@ __global__ void __launch_bounds__(NT) bn_bwd_kernel(const cvl_bf16* __restrict__
           vg[q] = ld_rows(dy + off[q]);
           if (PASS != 2) vz[q] = ld_rows(z + off[q]);
           if (use_y) vy[q] = ld_rows(y + off[q]);
+          if (use_b) vb[q] = reinterpret_cast<const uint8_t*>(y)[off[q] >> 3];
           if (SC) vs[q] = ld_rows(pg.sc_z + off[q]);
         }
 #pragma unroll
@@ -573,6 +588,9 @@ __global__ void __launch_bounds__(NT) bn_bwd_kernel(const cvl_bf16* __restrict__
             unpack8(vy[q], yy);
 #pragma unroll
             for (int u = 0; u < 8; ++u) g[u] = (yy[u] > 0.f && yy[u] < act_hi) ? g[u] : 0.f;   // ReLU / ReLU6
+          } else if (use_b) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) g[u] = ((vb[q] >> u) & 1u) ? g[u] : 0.f;
           } else if (zmask) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -1589,7 +1607,25 @@ extern "C" int cvl_bn_apply(const void* z, const float* mean_rstd, const float* 
   const int rpb = bn_rows_per_blk(B, HW, C);
   hipLaunchKernelGGL(bn_apply_kernel<false>, dim3((HW + rpb - 1) / rpb, B), dim3(NT), 0, S_, (const cvl_bf16*)z,
                      mean_rstd, gamma, beta, (const cvl_bf16*)residual, (cvl_bf16*)y, C, HW, relu, rpb,
-                     BnFin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 1}, BnRes{});
+                     BnFin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 1}, BnRes{}, (uint8_t*)nullptr);
+  return cvl_launch_status();
+}
+
+// `bits` (optional): the ReLU sign bitmap of y, uint8 [B*HW][C/8], for the BN backward's bitmap forms
+static int bn_finalize_apply_impl(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                  const void* z, const float* gamma, const float* beta, const void* residual,
+                                  void* y, uint8_t* bits, int B, int HW, int C, int relu, float eps, float momentum,
+                                  cvl_stream_t stream) {
+  CVL_CHECK_ARG(stats && mean_rstd && z && gamma && beta && y && C % 8 == 0 && B > 0 && HW > 0);
+  CVL_CHECK_ARG(C <= BN_FIN_MAXC);
+  CVL_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr));
+  const int dst = acc_decode_launch((acc_u64*)stats, 2L * B * C, S_);    // once per statistic, not per block
+  if (dst) return dst;
+  const int rpb = bn_rows_per_blk(B, HW, C);
+  auto k = bits ? bn_apply_kernel<true, false, true> : bn_apply_kernel<true>;
+  hipLaunchKernelGGL(k, dim3((HW + rpb - 1) / rpb, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)z,
+                     (const float*)nullptr, gamma, beta, (const cvl_bf16*)residual, (cvl_bf16*)y, C, HW, relu, rpb,
+                     BnFin{(const acc_u64*)stats, mean_rstd, run_mean, run_var, eps, momentum, g_acc_slots}, BnRes{}, bits);
   return cvl_launch_status();
 }
 
@@ -1597,24 +1633,25 @@ extern "C" int cvl_bn_finalize_apply(uint64_t* stats, float* mean_rstd, float* r
                                      const void* z, const float* gamma, const float* beta, const void* residual,
                                      void* y, int B, int HW, int C, int relu, float eps, float momentum,
                                      cvl_stream_t stream) {
-  CVL_CHECK_ARG(stats && mean_rstd && z && gamma && beta && y && C % 8 == 0 && B > 0 && HW > 0);
-  CVL_CHECK_ARG(C <= BN_FIN_MAXC);
-  CVL_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr));
-  const int dst = acc_decode_launch((acc_u64*)stats, 2L * B * C, S_);    // once per statistic, not per block
-  if (dst) return dst;
-  const int rpb = bn_rows_per_blk(B, HW, C);
-  hipLaunchKernelGGL(bn_apply_kernel<true>, dim3((HW + rpb - 1) / rpb, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)z,
-                     (const float*)nullptr, gamma, beta, (const cvl_bf16*)residual, (cvl_bf16*)y, C, HW, relu, rpb,
-                     BnFin{(const acc_u64*)stats, mean_rstd, run_mean, run_var, eps, momentum, g_acc_slots}, BnRes{});
-  return cvl_launch_status();
+  return bn_finalize_apply_impl(stats, mean_rstd, run_mean, run_var, z, gamma, beta, residual, y, nullptr, B, HW, C,
+                                relu, eps, momentum, stream);
 }
 
-extern "C" int cvl_bn_finalize_apply_bnres(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
-                                           const void* z, const float* gamma, const float* beta, uint64_t* res_stats,
-                                           float* res_mean_rstd, float* res_run_mean, float* res_run_var,
-                                           const void* res_z, const float* res_gamma, const float* res_beta,
-                                           float res_eps, float res_momentum, void* y, int B, int HW, int C, int relu,
-                                           float eps, float momentum, cvl_stream_t stream) {
+extern "C" int cvl_bn_finalize_apply_bits(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                          const void* z, const float* gamma, const float* beta,
+                                          const void* residual, void* y, uint8_t* relu_bits, int B, int HW, int C,
+                                          int relu, float eps, float momentum, cvl_stream_t stream) {
+  CVL_CHECK_ARG(relu_bits && relu == 1);
+  return bn_finalize_apply_impl(stats, mean_rstd, run_mean, run_var, z, gamma, beta, residual, y, relu_bits, B, HW,
+                                C, relu, eps, momentum, stream);
+}
+
+static int bn_finalize_apply_bnres_impl(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                        const void* z, const float* gamma, const float* beta, uint64_t* res_stats,
+                                        float* res_mean_rstd, float* res_run_mean, float* res_run_var,
+                                        const void* res_z, const float* res_gamma, const float* res_beta,
+                                        float res_eps, float res_momentum, void* y, uint8_t* bits, int B, int HW,
+                                        int C, int relu, float eps, float momentum, cvl_stream_t stream) {
   CVL_CHECK_ARG(stats && mean_rstd && z && gamma && beta && y && C % 8 == 0 && B > 0 && HW > 0);
   CVL_CHECK_ARG(res_stats && res_mean_rstd && res_z && res_gamma && res_beta);
   CVL_CHECK_ARG(C <= BN_FIN_MAXC);
@@ -1624,13 +1661,38 @@ extern "C" int cvl_bn_finalize_apply_bnres(uint64_t* stats, float* mean_rstd, fl
   if (!dst) dst = acc_decode_launch((acc_u64*)res_stats, 2L * B * C, S_);
   if (dst) return dst;
   const int rpb = bn_rows_per_blk(B, HW, C);
-  hipLaunchKernelGGL((bn_apply_kernel<true, true>), dim3((HW + rpb - 1) / rpb, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)z,
+  auto k = bits ? bn_apply_kernel<true, true, true> : bn_apply_kernel<true, true>;
+  hipLaunchKernelGGL(k, dim3((HW + rpb - 1) / rpb, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)z,
                      (const float*)nullptr, gamma, beta, (const cvl_bf16*)nullptr, (cvl_bf16*)y, C, HW, relu, rpb,
                      BnFin{(const acc_u64*)stats, mean_rstd, run_mean, run_var, eps, momentum, g_acc_slots},
                      BnRes{(const cvl_bf16*)res_z, res_gamma, res_beta,
                            BnFin{(const acc_u64*)res_stats, res_mean_rstd, res_run_mean, res_run_var, res_eps,
-                                 res_momentum, g_acc_slots}});
+                                 res_momentum, g_acc_slots}}, bits);
   return cvl_launch_status();
+}
+
+extern "C" int cvl_bn_finalize_apply_bnres(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                           const void* z, const float* gamma, const float* beta, uint64_t* res_stats,
+                                           float* res_mean_rstd, float* res_run_mean, float* res_run_var,
+                                           const void* res_z, const float* res_gamma, const float* res_beta,
+                                           float res_eps, float res_momentum, void* y, int B, int HW, int C, int relu,
+                                           float eps, float momentum, cvl_stream_t stream) {
+  return bn_finalize_apply_bnres_impl(stats, mean_rstd, run_mean, run_var, z, gamma, beta, res_stats, res_mean_rstd,
+                                      res_run_mean, res_run_var, res_z, res_gamma, res_beta, res_eps, res_momentum, y,
+                                      nullptr, B, HW, C, relu, eps, momentum, stream);
+}
+
+extern "C" int cvl_bn_finalize_apply_bnres_bits(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                                const void* z, const float* gamma, const float* beta,
+                                                uint64_t* res_stats, float* res_mean_rstd, float* res_run_mean,
+                                                float* res_run_var, const void* res_z, const float* res_gamma,
+                                                const float* res_beta, float res_eps, float res_momentum, void* y,
+                                                uint8_t* relu_bits, int B, int HW, int C, int relu, float eps,
+                                                float momentum, cvl_stream_t stream) {
+  CVL_CHECK_ARG(relu_bits && relu == 1);
+  return bn_finalize_apply_bnres_impl(stats, mean_rstd, run_mean, run_var, z, gamma, beta, res_stats, res_mean_rstd,
+                                      res_run_mean, res_run_var, res_z, res_gamma, res_beta, res_eps, res_momentum, y,
+                                      relu_bits, B, HW, C, relu, eps, momentum, stream);
 }
 
 extern "C" size_t cvl_bn_backward_workspace_size(int B, int HW, int C) {
@@ -1644,7 +1706,8 @@ extern "C" size_t cvl_bn_backward_workspace_size(int B, int HW, int C) {
 static int bn_backward_impl(const void* dy, const void* y_relu, const float* bn_beta, const void* z,
                             const float* mean_rstd, const float* gamma, void* workspace, size_t workspace_bytes,
                             void* dz, void* g_out, float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
-                            int B, int HW, int C, cvl_stream_t stream, float act_hi = INFINITY) {
+                            int B, int HW, int C, cvl_stream_t stream, float act_hi = INFINITY,
+                            bool y_bits = false) {       // y_bits: y_relu is the ReLU sign bitmap (MASK 4)
   CVL_CHECK_ARG(dy && z && mean_rstd && gamma && workspace && dz && dgamma && dbeta && C % 8 == 0);
   CVL_CHECK_ARG(B > 0 && HW > 0);
   CVL_CHECK_ARG(workspace_bytes >= cvl_bn_backward_workspace_size(B, HW, C));
@@ -1656,8 +1719,8 @@ static int bn_backward_impl(const void* dy, const void* y_relu, const float* bn_
   float* part0 = reinterpret_cast<float*>(dbsum + 2 * (size_t)C);
   dim3 g1(nchunk, B);
   const bool ym = y_relu != nullptr, zm = !ym && bn_beta != nullptr;
-  auto k0 = ym ? bn_bwd_kernel<0, 1> : zm ? bn_bwd_kernel<0, 2> : bn_bwd_kernel<0, 3>;
-  auto k1 = ym ? bn_bwd_kernel<1, 1> : zm ? bn_bwd_kernel<1, 2> : bn_bwd_kernel<1, 3>;
+  auto k0 = ym ? (y_bits ? bn_bwd_kernel<0, 4> : bn_bwd_kernel<0, 1>) : zm ? bn_bwd_kernel<0, 2> : bn_bwd_kernel<0, 3>;
+  auto k1 = ym ? (y_bits ? bn_bwd_kernel<1, 4> : bn_bwd_kernel<1, 1>) : zm ? bn_bwd_kernel<1, 2> : bn_bwd_kernel<1, 3>;
   hipLaunchKernelGGL(k0, g1, dim3(NT), 0, S_, (const cvl_bf16*)dy, (const cvl_bf16*)y_relu,
                      (const cvl_bf16*)z, mean_rstd, gamma, (const acc_u64*)nullptr, (cvl_bf16*)nullptr,
                      (cvl_bf16*)nullptr, part0, C, HW, rpb, 1, 0.f, BnPG{}, bn_beta, act_hi);
@@ -1678,6 +1741,16 @@ extern "C" int cvl_bn_backward(const void* dy, const void* y_relu, const void* z
                                int C, cvl_stream_t stream) {
   return bn_backward_impl(dy, y_relu, nullptr, z, mean_rstd, gamma, workspace, workspace_bytes, dz, g_out, dgamma,
                           dbeta, beta_acc, conv_dbias, B, HW, C, stream);
+}
+
+// cvl_bn_backward of a ReLU unit whose mask comes from the sign bitmap of y (cvl_bn_finalize_apply_bits)
+extern "C" int cvl_bn_backward_bits(const void* dy, const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                                    const float* gamma, void* workspace, size_t workspace_bytes, void* dz,
+                                    void* g_out, float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
+                                    int B, int HW, int C, cvl_stream_t stream) {
+  CVL_CHECK_ARG(relu_bits);
+  return bn_backward_impl(dy, relu_bits, nullptr, z, mean_rstd, gamma, workspace, workspace_bytes, dz, g_out, dgamma,
+                          dbeta, beta_acc, conv_dbias, B, HW, C, stream, INFINITY, true);
 }
 
 extern "C" int cvl_bn_backward_relu(const void* dy, const void* z, const float* mean_rstd, const float* gamma,
@@ -1719,20 +1792,38 @@ extern "C" int cvl_bn_backward_relu_sums(const void* dy, const void* z, const fl
 
 // Second pass only for a residual unit (mask y > 0, g_out = the masked gradient for the shortcut),
 // from the (sum g, sum g*xhat) the producing data gradient formed (cvl_conv_igemm_dgrad_bnsum_res).
-extern "C" int cvl_bn_backward_res_sums(const void* dy, const void* y, const void* z, const float* mean_rstd,
-                                        const float* gamma, uint64_t* sums, void* dz, void* g_out,
-                                        float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, int B,
-                                        int HW, int C, cvl_stream_t stream) {
+// (y_bits: `y` is the ReLU sign bitmap of y, uint8 [B*HW][C/8] -- the *_bits entries)
+static int bn_backward_res_sums_impl(const void* dy, const void* y, bool y_bits, const void* z,
+                                     const float* mean_rstd, const float* gamma, uint64_t* sums, void* dz,
+                                     void* g_out, float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
+                                     int B, int HW, int C, cvl_stream_t stream) {
   CVL_CHECK_ARG(dy && y && z && mean_rstd && gamma && sums && dz && dgamma && dbeta && C % 8 == 0);
   CVL_CHECK_ARG(B > 0 && HW > 0);
   const int dst = acc_decode_launch((acc_u64*)sums, 2L * B * C, S_);
   if (dst) return dst;
   const int rpb = bn1_rows_per_blk(B, HW, C);
   const int nchunk = (HW + rpb - 1) / rpb;
-  hipLaunchKernelGGL((bn_bwd_kernel<1, 1>), dim3(nchunk, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy, (const cvl_bf16*)y,
+  auto k1 = y_bits ? bn_bwd_kernel<1, 4> : bn_bwd_kernel<1, 1>;
+  hipLaunchKernelGGL(k1, dim3(nchunk, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy, (const cvl_bf16*)y,
                      (const cvl_bf16*)z, mean_rstd, gamma, (const acc_u64*)sums, (cvl_bf16*)dz, (cvl_bf16*)g_out, (float*)nullptr,
                      C, HW, rpb, 1, 0.f, BnPG{dgamma, dbeta, conv_dbias, beta_acc, nullptr, g_acc_slots}, (const float*)nullptr, INFINITY);
   return cvl_launch_status();
+}
+
+extern "C" int cvl_bn_backward_res_sums(const void* dy, const void* y, const void* z, const float* mean_rstd,
+                                        const float* gamma, uint64_t* sums, void* dz, void* g_out,
+                                        float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, int B,
+                                        int HW, int C, cvl_stream_t stream) {
+  return bn_backward_res_sums_impl(dy, y, false, z, mean_rstd, gamma, sums, dz, g_out, dgamma, dbeta, beta_acc,
+                                   conv_dbias, B, HW, C, stream);
+}
+
+extern "C" int cvl_bn_backward_res_sums_bits(const void* dy, const uint8_t* relu_bits, const void* z,
+                                             const float* mean_rstd, const float* gamma, uint64_t* sums, void* dz,
+                                             void* g_out, float* dgamma, float* dbeta, float beta_acc,
+                                             float* conv_dbias, int B, int HW, int C, cvl_stream_t stream) {
+  return bn_backward_res_sums_impl(dy, relu_bits, true, z, mean_rstd, gamma, sums, dz, g_out, dgamma, dbeta, beta_acc,
+                                   conv_dbias, B, HW, C, stream);
 }
 
 // A projection block's residual unit (Keras block1 conv3 BN -> + shortcut BN -> ReLU): the second pass
@@ -1746,12 +1837,12 @@ extern "C" size_t cvl_bn_backward_res_sums_sc_workspace_size(int B, int HW, int 
   return sizeof(float) * 2 * (size_t)B * ((HW + rpb - 1) / rpb) * C;
 }
 
-extern "C" int cvl_bn_backward_res_sums_sc(const void* dy, const void* y, const void* z, const float* mean_rstd,
-                                           const float* gamma, uint64_t* sums, void* dz, void* g_out,
-                                           float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
-                                           const void* z_sc, const float* mean_rstd_sc, void* workspace,
-                                           size_t workspace_bytes, uint64_t* sc_sums, int B, int HW, int C,
-                                           cvl_stream_t stream) {
+static int bn_backward_res_sums_sc_impl(const void* dy, const void* y, bool y_bits, const void* z,
+                                        const float* mean_rstd, const float* gamma, uint64_t* sums, void* dz,
+                                        void* g_out, float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
+                                        const void* z_sc, const float* mean_rstd_sc, void* workspace,
+                                        size_t workspace_bytes, uint64_t* sc_sums, int B, int HW, int C,
+                                        cvl_stream_t stream) {
   CVL_CHECK_ARG(dy && y && z && mean_rstd && gamma && sums && dz && g_out && dgamma && dbeta && C % 8 == 0);
   CVL_CHECK_ARG(z_sc && mean_rstd_sc && workspace && sc_sums && B > 0 && HW > 0);
   CVL_CHECK_ARG(workspace_bytes >= cvl_bn_backward_res_sums_sc_workspace_size(B, HW, C));
@@ -1763,12 +1854,35 @@ extern "C" int cvl_bn_backward_res_sums_sc(const void* dy, const void* y, const 
   BnPG pg{dgamma, dbeta, conv_dbias, beta_acc, nullptr, g_acc_slots};
   pg.sc_z = (const cvl_bf16*)z_sc;
   pg.sc_mr = mean_rstd_sc;
-  hipLaunchKernelGGL((bn_bwd_kernel<1, 1, true>), dim3(nchunk, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy,
+  auto k1 = y_bits ? bn_bwd_kernel<1, 4, true> : bn_bwd_kernel<1, 1, true>;
+  hipLaunchKernelGGL(k1, dim3(nchunk, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy,
                      (const cvl_bf16*)y, (const cvl_bf16*)z, mean_rstd, gamma, (const acc_u64*)sums, (cvl_bf16*)dz,
                      (cvl_bf16*)g_out, part, C, HW, rpb, 1, 0.f, pg, (const float*)nullptr, INFINITY);
   hipLaunchKernelGGL(bn_colsum_kernel, dim3((C + 31) / 32, B), dim3(NT), 0, S_, (const float*)part, nchunk, C,
                      (acc_u64*)sc_sums, 1);
   return cvl_launch_status();
+}
+
+extern "C" int cvl_bn_backward_res_sums_sc(const void* dy, const void* y, const void* z, const float* mean_rstd,
+                                           const float* gamma, uint64_t* sums, void* dz, void* g_out,
+                                           float* dgamma, float* dbeta, float beta_acc, float* conv_dbias,
+                                           const void* z_sc, const float* mean_rstd_sc, void* workspace,
+                                           size_t workspace_bytes, uint64_t* sc_sums, int B, int HW, int C,
+                                           cvl_stream_t stream) {
+  return bn_backward_res_sums_sc_impl(dy, y, false, z, mean_rstd, gamma, sums, dz, g_out, dgamma, dbeta, beta_acc,
+                                      conv_dbias, z_sc, mean_rstd_sc, workspace, workspace_bytes, sc_sums, B, HW, C,
+                                      stream);
+}
+
+extern "C" int cvl_bn_backward_res_sums_sc_bits(const void* dy, const uint8_t* relu_bits, const void* z,
+                                                const float* mean_rstd, const float* gamma, uint64_t* sums, void* dz,
+                                                void* g_out, float* dgamma, float* dbeta, float beta_acc,
+                                                float* conv_dbias, const void* z_sc, const float* mean_rstd_sc,
+                                                void* workspace, size_t workspace_bytes, uint64_t* sc_sums, int B,
+                                                int HW, int C, cvl_stream_t stream) {
+  return bn_backward_res_sums_sc_impl(dy, relu_bits, true, z, mean_rstd, gamma, sums, dz, g_out, dgamma, dbeta,
+                                      beta_acc, conv_dbias, z_sc, mean_rstd_sc, workspace, workspace_bytes, sc_sums,
+                                      B, HW, C, stream);
 }
 
 // The same for a residual unit whose first pass is NOT fused upstream (the small-map projection
@@ -1779,11 +1893,11 @@ extern "C" size_t cvl_bn_backward_sc_workspace_size(int B, int HW, int C) {
   return cvl_bn_backward_workspace_size(B, HW, C) + cvl_bn_backward_res_sums_sc_workspace_size(B, HW, C);
 }
 
-extern "C" int cvl_bn_backward_sc(const void* dy, const void* y, const void* z, const float* mean_rstd,
-                                  const float* gamma, void* workspace, size_t workspace_bytes, void* dz, void* g_out,
-                                  float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, const void* z_sc,
-                                  const float* mean_rstd_sc, uint64_t* sc_sums, int B, int HW, int C,
-                                  cvl_stream_t stream) {
+static int bn_backward_sc_impl(const void* dy, const void* y, bool y_bits, const void* z, const float* mean_rstd,
+                               const float* gamma, void* workspace, size_t workspace_bytes, void* dz, void* g_out,
+                               float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, const void* z_sc,
+                               const float* mean_rstd_sc, uint64_t* sc_sums, int B, int HW, int C,
+                               cvl_stream_t stream) {
   CVL_CHECK_ARG(dy && y && z && mean_rstd && gamma && workspace && dz && g_out && dgamma && dbeta && C % 8 == 0);
   CVL_CHECK_ARG(z_sc && mean_rstd_sc && sc_sums && B > 0 && HW > 0);
   CVL_CHECK_ARG(workspace_bytes >= cvl_bn_backward_sc_workspace_size(B, HW, C));
@@ -1793,7 +1907,9 @@ extern "C" int cvl_bn_backward_sc(const void* dy, const void* y, const void* z, 
   double* dbsum = reinterpret_cast<double*>(sums + 2 * (size_t)B * C);
   float* part0 = reinterpret_cast<float*>(dbsum + 2 * (size_t)C);
   float* part_sc = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + cvl_bn_backward_workspace_size(B, HW, C));
-  hipLaunchKernelGGL((bn_bwd_kernel<0, 1>), dim3(nchunk, B), dim3(NT), 0, S_, (const cvl_bf16*)dy, (const cvl_bf16*)y,
+  auto k0 = y_bits ? bn_bwd_kernel<0, 4> : bn_bwd_kernel<0, 1>;
+  auto k1 = y_bits ? bn_bwd_kernel<1, 4, true> : bn_bwd_kernel<1, 1, true>;
+  hipLaunchKernelGGL(k0, dim3(nchunk, B), dim3(NT), 0, S_, (const cvl_bf16*)dy, (const cvl_bf16*)y,
                      (const cvl_bf16*)z, mean_rstd, gamma, (const acc_u64*)nullptr, (cvl_bf16*)nullptr,
                      (cvl_bf16*)nullptr, part0, C, HW, rpb, 1, 0.f, BnPG{}, (const float*)nullptr, INFINITY);
   hipLaunchKernelGGL(bn_colsum_kernel, dim3((C + 31) / 32, B), dim3(NT), 0, S_, (const float*)part0, nchunk, C,
@@ -1803,12 +1919,31 @@ extern "C" int cvl_bn_backward_sc(const void* dy, const void* y, const void* z, 
   BnPG pg{dgamma, dbeta, conv_dbias, beta_acc, nullptr, 1};
   pg.sc_z = (const cvl_bf16*)z_sc;
   pg.sc_mr = mean_rstd_sc;
-  hipLaunchKernelGGL((bn_bwd_kernel<1, 1, true>), dim3(nchunk1, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy,
+  hipLaunchKernelGGL(k1, dim3(nchunk1, B + 1), dim3(NT), 0, S_, (const cvl_bf16*)dy,
                      (const cvl_bf16*)y, (const cvl_bf16*)z, mean_rstd, gamma, (const acc_u64*)sums, (cvl_bf16*)dz,
                      (cvl_bf16*)g_out, part_sc, C, HW, rpb1, 1, 0.f, pg, (const float*)nullptr, INFINITY);
   hipLaunchKernelGGL(bn_colsum_kernel, dim3((C + 31) / 32, B), dim3(NT), 0, S_, (const float*)part_sc, nchunk1, C,
                      (acc_u64*)sc_sums, 1);
   return cvl_launch_status();
+}
+
+extern "C" int cvl_bn_backward_sc(const void* dy, const void* y, const void* z, const float* mean_rstd,
+                                  const float* gamma, void* workspace, size_t workspace_bytes, void* dz, void* g_out,
+                                  float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, const void* z_sc,
+                                  const float* mean_rstd_sc, uint64_t* sc_sums, int B, int HW, int C,
+                                  cvl_stream_t stream) {
+  return bn_backward_sc_impl(dy, y, false, z, mean_rstd, gamma, workspace, workspace_bytes, dz, g_out, dgamma, dbeta,
+                             beta_acc, conv_dbias, z_sc, mean_rstd_sc, sc_sums, B, HW, C, stream);
+}
+
+extern "C" int cvl_bn_backward_sc_bits(const void* dy, const uint8_t* relu_bits, const void* z,
+                                       const float* mean_rstd, const float* gamma, void* workspace,
+                                       size_t workspace_bytes, void* dz, void* g_out, float* dgamma, float* dbeta,
+                                       float beta_acc, float* conv_dbias, const void* z_sc,
+                                       const float* mean_rstd_sc, uint64_t* sc_sums, int B, int HW, int C,
+                                       cvl_stream_t stream) {
+  return bn_backward_sc_impl(dy, relu_bits, true, z, mean_rstd, gamma, workspace, workspace_bytes, dz, g_out, dgamma,
+                             dbeta, beta_acc, conv_dbias, z_sc, mean_rstd_sc, sc_sums, B, HW, C, stream);
 }
 
 // Second pass only of a BN WITHOUT ReLU (the projection shortcut's BN) from first-pass sums [B][C][2]

@@ -47,6 +47,19 @@ SIGNATURES = {
     "cvl_conv_igemm_last_ktile": (c_int, []),
     "cvl_conv_igemm_plan": (c_int, [P, c_int, c_size_t, P, P]),
     "cvl_conv_kernel_name": (ctypes.c_char_p, [c_int]),
+    # the ReLU sign bitmap forms: as their namesakes, the bitmap in y's place (apply: after y)
+    "cvl_conv_igemm_plan_bnsum": (c_int, [P, c_int, c_size_t, P, P, P]),
+    "cvl_conv_igemm_dgrad_bnsum_res_bits": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]),
+    "cvl_bn_finalize_apply_bits": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float,
+                                           c_float, P]),
+    "cvl_bn_finalize_apply_bnres_bits": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_float, c_float, P, P,
+                                                 c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    "cvl_bn_backward_bits": (c_int, [P, P, P, P, P, P, c_size_t, P, P, P, P, c_float, P, c_int, c_int, c_int, P]),
+    "cvl_bn_backward_res_sums_bits": (c_int, [P, P, P, P, P, P, P, P, P, P, c_float, P, c_int, c_int, c_int, P]),
+    "cvl_bn_backward_res_sums_sc_bits": (c_int, [P, P, P, P, P, P, P, P, P, P, c_float, P, P, P, P, c_size_t, P,
+                                                 c_int, c_int, c_int, P]),
+    "cvl_bn_backward_sc_bits": (c_int, [P, P, P, P, P, P, c_size_t, P, P, P, P, c_float, P, P, P, P, c_int, c_int,
+                                        c_int, P]),
     "cvl_centernet_peak_decode_workspace_size": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "cvl_centernet_peak_decode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, P, P, P,
                                           ctypes.c_size_t, P]),
@@ -208,7 +221,10 @@ _lib = None
 
 
 # test / profiling queries that a CVL_LIB build of the parent revision (tools/build_base.sh) may lack
-NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan"}
+NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_plan_bnsum",
+         "cvl_conv_igemm_dgrad_bnsum_res_bits", "cvl_bn_finalize_apply_bits", "cvl_bn_finalize_apply_bnres_bits",
+         "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
+         "cvl_bn_backward_sc_bits"}
 
 
 def load():

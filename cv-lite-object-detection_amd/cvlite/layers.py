@@ -256,6 +256,9 @@ FUSE_BNSUM = not _lib.dispatch("no_bnsum_fuse")
 FUSE_BNSUM_RES = FUSE_BNSUM and not _lib.dispatch("no_bnsum_res")
 # ... and a projection shortcut BN's first pass into the residual unit's second pass (no_sc_bnsum: off)
 FUSE_SC_BNSUM = FUSE_BNSUM_RES and not _lib.dispatch("no_sc_bnsum")
+# a residual unit's forward also writes the ReLU sign bitmap of its output (1 bit per element), which
+# the BN backward and the fused residual data gradient read instead of y (CVL_DISPATCH=no_relu_bits: off)
+RELU_BITS = not _lib.dispatch("no_relu_bits")
 
 # Batched weight gradients (round 6; CVL_DISPATCH=no_wgrad_batch: off).  Inside `with wgrad_batch():`
 # Conv.wgrad collects its 1x1 / 3x3 bf16 problems (keeping their x / dy alive) instead of launching
@@ -347,6 +350,8 @@ class BatchNorm(object):
         residual_bn: a deferred unit's (z, stats, mean_rstd out, BatchNorm) -- the residual is that
         BN's output, formed in the same launch (cvl_bn_finalize_apply_bnres), never stored."""
         y = torch.empty_like(z)
+        if train and relu == 1 and RELU_BITS and (residual is not None or residual_bn is not None):
+            nn.attach_relu_bits(y)              # filled by the finalize + apply launch below
         if train and residual_bn is not None:
             rz, rstats, rmr, rbn = residual_bn
             mr = torch.empty((B, self.c, 2), dtype=torch.float32, device=z.device)

@@ -342,8 +342,33 @@ def bn_apply(z, mean_rstd, gamma, beta, residual, y, B, HW, C, relu):
               B, HW, C, int(relu), stream())          # relu: 0 none, 1 ReLU, 2 ReLU6
 
 
+# A residual unit's ReLU sign bitmap (uint8 [B*HW][C/8], bit u of a byte = y[8c + u] > 0) travels as an
+# attribute of the y tensor it describes: the forward entries below write it when y carries one, the
+# residual BN-backward entries and the fused 1x1 data gradient read it in place of y.  A view or copy of
+# y is another tensor object and carries none (then the y forms run).
+def attach_relu_bits(y):
+    """Allocate y's ReLU sign bitmap and attach it; the next bn_finalize_apply[_bnres] into y fills it.
+    None (nothing attached) for layouts without whole 8-channel chunks, fp32, or a library without
+    the bitmap entries (an A/B build of an earlier revision)."""
+    if y.dtype != torch.bfloat16 or y.shape[-1] % 8 or not hasattr(_lib.load(), "cvl_bn_finalize_apply_bits"):
+        return None
+    y._cvl_relu_bits = torch.empty(y.numel() // 8, dtype=torch.uint8, device=y.device)
+    return y._cvl_relu_bits
+
+
+def relu_bits(y):
+    """The bitmap attached to y (attach_relu_bits), or None."""
+    return getattr(y, "_cvl_relu_bits", None) if y is not None else None
+
+
 def bn_finalize_apply(stats, mean_rstd, run_mean, run_var, z, gamma, beta, residual, y, B, HW, C, relu, eps,
                       momentum):
+    bits = relu_bits(y)
+    if bits is not None and int(relu) == 1 and not _is_f32(z):
+        _lib.call("cvl_bn_finalize_apply_bits", acc_ptr(stats), ptr(mean_rstd), ptr(run_mean), ptr(run_var), ptr(z),
+                  ptr(gamma), ptr(beta), ptr(residual), ptr(y), ptr(bits), B, HW, C, int(relu), float(eps),
+                  float(momentum), stream())
+        return
     _lib.call("cvl_bn_finalize_apply_f32" if _is_f32(z) else "cvl_bn_finalize_apply", acc_ptr(stats), ptr(mean_rstd), ptr(run_mean), ptr(run_var), ptr(z), ptr(gamma),
               ptr(beta), ptr(residual), ptr(y), B, HW, C, int(relu), float(eps), float(momentum), stream())
 
@@ -352,6 +377,13 @@ def bn_finalize_apply_bnres(stats, mean_rstd, run_mean, run_var, z, gamma, beta,
                             res_run_mean, res_run_var, res_z, res_gamma, res_beta, res_eps, res_momentum, y, B,
                             HW, C, relu, eps, momentum):
     """y = act(BN(z) + BN_res(res_z)) with both finalizes in one launch (cvl_bn_finalize_apply_bnres)."""
+    bits = relu_bits(y)
+    if bits is not None and int(relu) == 1:
+        _lib.call("cvl_bn_finalize_apply_bnres_bits", acc_ptr(stats), ptr(mean_rstd), ptr(run_mean), ptr(run_var),
+                  ptr(z), ptr(gamma), ptr(beta), acc_ptr(res_stats), ptr(res_mean_rstd), ptr(res_run_mean),
+                  ptr(res_run_var), ptr(res_z), ptr(res_gamma), ptr(res_beta), float(res_eps), float(res_momentum),
+                  ptr(y), ptr(bits), B, HW, C, int(relu), float(eps), float(momentum), stream())
+        return
     _lib.call("cvl_bn_finalize_apply_bnres", acc_ptr(stats), ptr(mean_rstd), ptr(run_mean), ptr(run_var), ptr(z),
               ptr(gamma), ptr(beta), acc_ptr(res_stats), ptr(res_mean_rstd), ptr(res_run_mean), ptr(res_run_var),
               ptr(res_z), ptr(res_gamma), ptr(res_beta), float(res_eps), float(res_momentum), ptr(y), B, HW, C,
@@ -365,6 +397,12 @@ def bn_backward(dy, y_relu, z, mean_rstd, gamma, dz, g_out, dgamma, dbeta, B, HW
                                conv_dbias)
     n = int(_lib.load().cvl_bn_backward_workspace_size(B, HW, C))
     ws = torch.empty(n, dtype=torch.uint8, device=dy.device)
+    bits = relu_bits(y_relu)
+    if bits is not None:
+        _lib.call("cvl_bn_backward_bits", ptr(dy), ptr(bits), ptr(z), ptr(mean_rstd), ptr(gamma), ptr(ws), n,
+                  ptr(dz), ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), B, HW, C,
+                  stream())
+        return
     _lib.call("cvl_bn_backward", ptr(dy), ptr(y_relu), ptr(z), ptr(mean_rstd), ptr(gamma), ptr(ws), n,
               ptr(dz), ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), B, HW, C,
               stream())
@@ -444,6 +482,12 @@ def conv_igemm_dgrad_bnsum_res(desc, src, dst, y, z, mean_rstd, gamma, beta, sum
     if zero:
         sums.zero_()
     flag = ctypes.c_int32(0)
+    bits = relu_bits(y)
+    if bits is not None and not _is_f32(src):
+        _lib.call("cvl_conv_igemm_dgrad_bnsum_res_bits", ctypes.byref(desc), ptr(src), ptr(dst), ptr(y), ptr(bits),
+                  ptr(z), ptr(mean_rstd), ptr(gamma), ptr(beta), acc_ptr(sums), ctypes.addressof(flag), None,
+                  ptr(ws), n if ws is not None else 0, stream())
+        return bool(flag.value)
     _lib.call("cvl_conv_igemm_dgrad_bnsum_res", ctypes.byref(desc), ptr(src), ptr(dst), ptr(y), ptr(z),
               ptr(mean_rstd), ptr(gamma), ptr(beta), acc_ptr(sums), ctypes.addressof(flag), ptr(ws),
               n if ws is not None else 0, stream())
@@ -453,6 +497,12 @@ def conv_igemm_dgrad_bnsum_res(desc, src, dst, y, z, mean_rstd, gamma, beta, sum
 def bn_backward_res_sums(dy, y, z, mean_rstd, gamma, sums, dz, g_out, dgamma, dbeta, B, HW, C, beta_acc=0.0,
                          conv_dbias=None):
     """Second pass of a residual unit's BN backward (mask y > 0, g_out = masked dy) from the fused sums."""
+    bits = relu_bits(y)
+    if bits is not None:
+        _lib.call("cvl_bn_backward_res_sums_bits", ptr(dy), ptr(bits), ptr(z), ptr(mean_rstd), ptr(gamma),
+                  acc_ptr(sums), ptr(dz), ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), B,
+                  HW, C, stream())
+        return
     _lib.call("cvl_bn_backward_res_sums", ptr(dy), ptr(y), ptr(z), ptr(mean_rstd), ptr(gamma), acc_ptr(sums), ptr(dz),
               ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), B, HW, C, stream())
 
@@ -463,7 +513,9 @@ def bn_backward_res_sums_sc(dy, y, z, mean_rstd, gamma, sums, dz, g_out, dgamma,
     into sc_sums [B][C][2] (float64 values); bn_backward_sums then runs the shortcut's second pass."""
     n = int(_lib.load().cvl_bn_backward_res_sums_sc_workspace_size(B, HW, C))
     ws = torch.empty(n, dtype=torch.uint8, device=dy.device)
-    _lib.call("cvl_bn_backward_res_sums_sc", ptr(dy), ptr(y), ptr(z), ptr(mean_rstd), ptr(gamma), acc_ptr(sums),
+    bits = relu_bits(y)
+    _lib.call("cvl_bn_backward_res_sums_sc_bits" if bits is not None else "cvl_bn_backward_res_sums_sc", ptr(dy),
+              ptr(bits if bits is not None else y), ptr(z), ptr(mean_rstd), ptr(gamma), acc_ptr(sums),
               ptr(dz), ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), ptr(z_sc),
               ptr(mean_rstd_sc), ptr(ws), n, ptr(sc_sums), B, HW, C, stream())
 
@@ -474,7 +526,9 @@ def bn_backward_sc(dy, y, z, mean_rstd, gamma, dz, g_out, dgamma, dbeta, z_sc, m
     pass into sc_sums [B][C][2] (float64 values)."""
     n = int(_lib.load().cvl_bn_backward_sc_workspace_size(B, HW, C))
     ws = torch.empty(n, dtype=torch.uint8, device=dy.device)
-    _lib.call("cvl_bn_backward_sc", ptr(dy), ptr(y), ptr(z), ptr(mean_rstd), ptr(gamma), ptr(ws), n, ptr(dz),
+    bits = relu_bits(y)
+    _lib.call("cvl_bn_backward_sc_bits" if bits is not None else "cvl_bn_backward_sc", ptr(dy),
+              ptr(bits if bits is not None else y), ptr(z), ptr(mean_rstd), ptr(gamma), ptr(ws), n, ptr(dz),
               ptr(g_out), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(conv_dbias), ptr(z_sc), ptr(mean_rstd_sc),
               ptr(sc_sums), B, HW, C, stream())
 

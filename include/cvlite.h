@@ -394,6 +394,53 @@ int cvl_bn_backward_sums(const void* dy, const void* z, const float* mean_rstd, 
                          const uint64_t* sums, void* dz, float* dgamma, float* dbeta, float beta_acc,
                          float* conv_dbias, int B, int HW, int C, cvl_stream_t stream);
 
+/* The ReLU sign bitmap of a residual unit's output (no reference counterpart: the backward of
+ * y = relu(BN(z) + shortcut) uses only the sign of y).  relu_bits: uint8 [B*HW][C/8], dense; bit u of
+ * byte [row][c] is 1 where the STORED (bf16-rounded) y[row][8c + u] > 0.  bf16, relu == 1 only.
+ * cvl_bn_finalize_apply_bits / _bnres_bits: their namesakes, which also write relu_bits (y is
+ * bit-identical).  The *_bits backward entries: their namesakes with relu_bits in y's place (1/16 of
+ * the bytes; dz, g_out, sc_sums, dgamma, dbeta bit-identical).
+ * cvl_conv_igemm_dgrad_bnsum_res_bits: cvl_conv_igemm_dgrad_bnsum_res with the mask of the fused sums
+ * read from relu_bits (laid out as dst: byte (row * ld_dst + dst_coff + n) / 8, so ld_dst and
+ * dst_coff must be multiples of 8 -- otherwise the y form runs, hence y is still passed); *form
+ * (optional) = 3 bitmap form / 2 y form / 0 not fused.
+ * cvl_conv_igemm_plan_bnsum: host-only query, as cvl_conv_igemm_plan, for a fused BN-sums offer
+ * (1 z mask, 2 y mask, 3 bitmap): the form that would run (*form, 0 = none: the plain data gradient),
+ * kernel family and K-tile. */
+int cvl_bn_finalize_apply_bits(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var, const void* z,
+                               const float* gamma, const float* beta, const void* residual, void* y,
+                               uint8_t* relu_bits, int B, int HW, int C, int relu, float eps, float momentum,
+                               cvl_stream_t stream);
+int cvl_bn_finalize_apply_bnres_bits(uint64_t* stats, float* mean_rstd, float* run_mean, float* run_var,
+                                     const void* z, const float* gamma, const float* beta, uint64_t* res_stats,
+                                     float* res_mean_rstd, float* res_run_mean, float* res_run_var,
+                                     const void* res_z, const float* res_gamma, const float* res_beta,
+                                     float res_eps, float res_momentum, void* y, uint8_t* relu_bits, int B, int HW,
+                                     int C, int relu, float eps, float momentum, cvl_stream_t stream);
+int cvl_bn_backward_bits(const void* dy, const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                         const float* gamma, void* workspace, size_t workspace_bytes, void* dz, void* g_out,
+                         float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, int B, int HW, int C,
+                         cvl_stream_t stream);
+int cvl_bn_backward_res_sums_bits(const void* dy, const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                                  const float* gamma, uint64_t* sums, void* dz, void* g_out, float* dgamma,
+                                  float* dbeta, float beta_acc, float* conv_dbias, int B, int HW, int C,
+                                  cvl_stream_t stream);
+int cvl_bn_backward_res_sums_sc_bits(const void* dy, const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                                     const float* gamma, uint64_t* sums, void* dz, void* g_out, float* dgamma,
+                                     float* dbeta, float beta_acc, float* conv_dbias, const void* z_sc,
+                                     const float* mean_rstd_sc, void* workspace, size_t workspace_bytes,
+                                     uint64_t* sc_sums, int B, int HW, int C, cvl_stream_t stream);
+int cvl_bn_backward_sc_bits(const void* dy, const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                            const float* gamma, void* workspace, size_t workspace_bytes, void* dz, void* g_out,
+                            float* dgamma, float* dbeta, float beta_acc, float* conv_dbias, const void* z_sc,
+                            const float* mean_rstd_sc, uint64_t* sc_sums, int B, int HW, int C, cvl_stream_t stream);
+int cvl_conv_igemm_dgrad_bnsum_res_bits(const cvl_conv_desc* d, const void* src, void* dst, const void* y,
+                                        const uint8_t* relu_bits, const void* z, const float* mean_rstd,
+                                        const float* gamma, const float* beta, uint64_t* sums, int32_t* fused,
+                                        int32_t* form, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
+int cvl_conv_igemm_plan_bnsum(const cvl_conv_desc* d, int offer, size_t workspace_bytes, int32_t* form,
+                              int32_t* kernel, int32_t* ktile);
+
 /* BN -> ReLU6 unit without a residual (MobileNetV2: Keras ReLU(6.)): as cvl_bn_backward_relu with
  * the TF Relu6Grad mask 0 < bn(z) < 6 rebuilt from z in fp32 (the forward's exact pre-clamp value);
  * cvl_bn_apply / cvl_bn_finalize_apply take relu = 2 for ReLU6. */
