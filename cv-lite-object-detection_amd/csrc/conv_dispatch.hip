@@ -207,7 +207,9 @@ bool plan_p(const cvl_conv_desc* d, const ConvArgs& a, const ConvCallOpts& o, Co
   if (!use) return false;
   const int ntiles = a.m_tiles * (a.Npad / use);
   const int ntn = a.Npad / use;
-  int grid = cvl_tune_int("CVL_CONV_P_WGS", 256);
+  // (CVL_DISPATCH=p_wgs: a test hook -- several tiles per workgroup at small sizes; 1 .. 256)
+  const int wgs = cvl_dispatch_int("p_wgs", 256);
+  int grid = cvl_tune_int("CVL_CONV_P_WGS", wgs > 256 ? 256 : (wgs < 1 ? 1 : wgs));
   if (grid >= ntiles) grid = ntiles;
   else grid -= grid % ntn;                      // every workgroup keeps one N tile
   if (grid < 1) return false;

@@ -741,3 +741,23 @@ extern "C" int cvl_conv_igemm_plan_bnsum(const cvl_conv_desc* d, int offer, size
   *ktile = conv_plan_ktile(p);
   return CVL_OK;
 }
+
+// Test hook: cvl_conv_igemm_plan (offer 0) / cvl_conv_igemm_plan_bnsum (offer 1..3) with the planned
+// launch grid (*grid: workgroups per split) and N-tile width (*ntile) as well.  Host only, no launch.
+extern "C" int cvl_conv_igemm_plan_grid(const cvl_conv_desc* d, int with_bn_stats, int bsum_offer, size_t workspace_bytes,
+                                        int32_t* kernel, int32_t* ktile, int32_t* grid, int32_t* ntile) {
+  CVL_CHECK_ARG(d && kernel && ktile && grid && ntile && bsum_offer >= CVL_BSUM_NONE && bsum_offer <= CVL_BSUM_BITS);
+  *kernel = CVL_CK_NONE;
+  *ktile = *grid = *ntile = 0;
+  if (d->prec == CVL_PREC_F32) return CVL_OK;
+  int32_t form = CVL_BSUM_NONE;
+  int st = bsum_offer ? dgrad_bnsum_plan_form(d, bsum_offer, workspace_bytes, &form) : CVL_OK;
+  if (st) return st;
+  ConvPlan p;
+  if ((st = conv_plan(d, ConvCallOpts{with_bn_stats != 0 && !form, form, false, workspace_bytes}, &p))) return st;
+  *kernel = p.kernel;
+  *ktile = conv_plan_ktile(p);
+  *grid = p.grid;
+  *ntile = p.bn;
+  return CVL_OK;
+}

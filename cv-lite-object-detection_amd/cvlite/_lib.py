@@ -46,6 +46,7 @@ SIGNATURES = {
     "cvl_conv_igemm_last_kernel": (c_int, []),
     "cvl_conv_igemm_last_ktile": (c_int, []),
     "cvl_conv_igemm_plan": (c_int, [P, c_int, c_size_t, P, P]),
+    "cvl_conv_igemm_plan_grid": (c_int, [P, c_int, c_int, c_size_t, P, P, P, P]),
     "cvl_conv_kernel_name": (ctypes.c_char_p, [c_int]),
     # the ReLU sign bitmap forms: as their namesakes, the bitmap in y's place (apply: after y)
     "cvl_conv_igemm_plan_bnsum": (c_int, [P, c_int, c_size_t, P, P, P]),
@@ -221,7 +222,7 @@ _lib = None
 
 
 # test / profiling queries that a CVL_LIB build of the parent revision (tools/build_base.sh) may lack
-NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_plan_bnsum",
+NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_plan_bnsum", "cvl_conv_igemm_plan_grid",
          "cvl_conv_igemm_dgrad_bnsum_res_bits", "cvl_bn_finalize_apply_bits", "cvl_bn_finalize_apply_bnres_bits",
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
          "cvl_bn_backward_sc_bits"}

@@ -207,6 +207,14 @@ int cvl_conv_igemm_last_ktile(void);
  * host code, no device memory, no launch.  CVL_EINVAL where cvl_conv_igemm would reject d. */
 int cvl_conv_igemm_plan(const cvl_conv_desc* d, int with_bn_stats, size_t workspace_bytes, int32_t* kernel,
                         int32_t* ktile);
+/* The same query with the launch geometry: *grid = the workgroups the launch would have (per K split),
+ * *ntile = its N-tile width in channels.  bsum_offer 0: a cvl_conv_igemm call; 1 / 2 / 3: a
+ * cvl_conv_igemm_dgrad_bnsum / _res / _res_bits call offering that fused BN-sums form (as
+ * cvl_conv_igemm_plan_bnsum; a declined offer reports the plain data gradient's plan).  For the
+ * persistent 1x1 kernel (CVL_CK_P) a workgroup walks ceil(m_tiles / (grid / (Npad / ntile))) 256-row
+ * tiles, so tests derive "several tiles per workgroup" from the planner's own answer.  Host only. */
+int cvl_conv_igemm_plan_grid(const cvl_conv_desc* d, int with_bn_stats, int bsum_offer, size_t workspace_bytes,
+                             int32_t* kernel, int32_t* ktile, int32_t* grid, int32_t* ntile);
 const char* cvl_conv_kernel_name(int code);
 
 /* Measurement hook (no reference counterpart: bench.py's in-step roofline timing).  cvl_probe_arm

@@ -2,7 +2,10 @@
 
 The 64-deep form multiplies the two 32-deep halves of a K-tile in k order, so its accumulation
 sequence is the 32-deep form's: every case runs with CVL_DISPATCH=p_k64=1 and =0 and compares the
-raw bits (outputs, BN statistics and fused BN-backward sums).  Every case also asserts
+raw bits (outputs, BN statistics and fused BN-backward sums).  The maps below have fewer tiles than
+the persistent grid, so every workgroup runs one tile; the (2, 32) map runs a second time with
+CVL_DISPATCH=p_wgs=4 (2 to 8 tiles per workgroup), which holds the identity across tiles as well
+(the cross-tile stream against fp64: tests/test_gpu_conv_p_stream.py).  Every case also asserts
 cvl_conv_igemm_last_ktile(), so a path that is silently not taken fails: 64 where K % 64 == 0, 32
 for K = 96 and with the flag off.  One forward and one data-gradient mode are checked against fp64
 as well (tolerances as tests/test_gpu_conv_production.py: one bf16 rounding of the result,
@@ -52,6 +55,9 @@ P_MODES = ["fwd_stats", "fwd_s2", "fwd_f32", "dgrad", "dgrad_beta", "dgrad_up2",
 # B, H: one tile per image and fewer tiles than workgroups; several tiles per image; ragged (M = 192:
 # one partly absent tile, no statistics)
 P_MAPS = [(3, 16), (2, 32), (3, 8)]
+# (B, H, p_wgs): every map on the default grid (256: one tile per workgroup at these sizes), then the
+# 8-tile map on 4 workgroups
+P_RUNS = [(B, H, 256) for B, H in P_MAPS] + [(2, 32, 4)]
 
 
 def p_case(mode, K, N, B, H):
@@ -120,12 +126,13 @@ def p_case(mode, K, N, B, H):
 @pytest.mark.parametrize("K", [64, 128, 192, 96])
 @pytest.mark.parametrize("mode", P_MODES)
 def test_p_k64_bit_identical_to_k32(dispatch, mode, K, N):
-    """K = 64: one K-tile per tile (the stream runs across tiles only); 128 = the ring depth D;
-    192: an odd count above D; 96: the 32-deep fallback.  N 64 / 128 / 256: the 64- and 128-wide
-    tiles (one and two B pieces per wave)."""
+    """K = 64: one K-tile per tile (with p_wgs=4 the stream runs across tiles only); 128 = the ring
+    depth D; 192: an odd count above D; 96: the 32-deep fallback.  N 64 / 128 / 256: the 64- and
+    128-wide tiles (one and two B pieces per wave)."""
     if mode == "bnsum_res":
         dispatch("bnsum_res_min_hw=0")
-    for B, H in P_MAPS:
+    for B, H, wgs in P_RUNS:
+        dispatch("p_wgs=%d" % wgs)
         if (H * H) % 256 and mode in ("bnsum", "bnsum_res"):
             continue                           # the fused sums need whole tiles per image
         run, ref = p_case(mode, K, N, B, H)
@@ -139,7 +146,7 @@ def test_p_k64_bit_identical_to_k32(dispatch, mode, K, N):
             torch.cuda.synchronize()
             res.append(r)
         for a, b in zip(*res):
-            assert torch.equal(bits(a), bits(b)), "%s K %d N %d B %d H %d" % (mode, K, N, B, H)
+            assert torch.equal(bits(a), bits(b)), "%s K %d N %d B %d H %d wgs %d" % (mode, K, N, B, H, wgs)
         if ref is not None:
             out = res[0][0].to(F64).view(ref.shape)
             torch.testing.assert_close(out, ref, rtol=1e-2, atol=2e-2)

@@ -75,3 +75,27 @@ def test_bn_affine_mask_is_fma_exact():
     a, xh = lp.bn_affine32(z, m, rs, ga, be)
     exact = ga.double() * ((z.float() - m) * rs).double() + be.double()
     assert torch.equal(a > 0, exact > 0)
+
+
+def test_row_err_sees_one_row_where_rel_l2_does_not():
+    """The worst-row criterion of the conv destinations: bf16 rounding stays below 2^-8 (two roundings:
+    2^-7), all-zero rows do not divide by nothing, and ONE wrong row of a large block -- which moves
+    the whole-tensor rel-L2 by far less than its tolerance -- scores above 1."""
+    g = torch.Generator().manual_seed(3)
+    ref = torch.randn((100000, 64), generator=g, dtype=torch.float64)
+    ref[100:200] = 0                                   # all-zero rows (the gap pixels of a strided data gradient)
+    ref[300] *= 1e-6                                   # a row far below the typical size
+    got = ref.to(torch.bfloat16)
+    assert lp.row_err(got, ref) <= 2.0 ** -8
+    old = torch.randn(ref.shape, generator=g, dtype=torch.float64).to(torch.bfloat16)
+    acc = (ref.to(torch.bfloat16).double() + old.double()).to(torch.bfloat16)
+    assert lp.row_err(acc, ref + old.double()) <= 2.0 ** -7
+    for bad_row in (got[4001].clone(), old[7], torch.zeros(64, dtype=torch.bfloat16)):
+        bad = got.clone()
+        bad[4000] = bad_row                            # a row one pixel off / left at its old value / unwritten
+        assert lp.rel_l2(bad, ref) < lp.TOL_BF16
+        assert lp.row_err(bad, ref) > 0.9
+    bad = got.clone()
+    bad[150, 3] = 0.5                                  # a store into a row that must stay zero
+    assert lp.row_err(bad, ref) > lp.TOL_BF16
+    assert lp.row_err(torch.zeros(4, 8), torch.zeros(4, 8)) == 0.0
