@@ -3,6 +3,7 @@
 #include "cvl_common.h"
 #include "bn_acc.h"
 #include <type_traits>
+#include <vector>
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -210,6 +211,94 @@ static inline void with_bool(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
 }
+
+// ---- weight-gradient dispatch (conv_wgrad_dispatch.hip) -------------------------------------------
+constexpr int kWgSegM = 128;        // segment / chunk alignment of the M space, every weight-gradient kernel
+constexpr int kWgXMaxGroups = 2;    // groups one X launch covers
+constexpr int kWgXMaxProb = 16, kWgHMaxProb = 12;   // problems per batched X / WH launch (kernel-argument bytes)
+
+// One launch of a weight-gradient call: the kernel, the segments it covers and the family's parameters.
+struct WgLaunch {
+  int kernel;               // CVL_CK_WG_*
+  int seg0, nseg, ngroups;  // segments [seg0, seg0 + nseg) of the call's descriptor, in ngroups equal groups
+  int tile;                 // co tile width: S 32 / 64 / 128, L 128 / 256, X 128 / 256
+  int rows;                 // reduction rows per step: S 64 / 128, X 32 / 64
+  bool pf;                  // X: the next step's fragments are read under this step's MFMAs
+  int tiles, co_tiles;      // output tiles per (group, split) and along co; SN: input-channel tiles
+  int chunk, nsplit;        // rows per split (WH: 128-row steps) and splits; SN: chunk rows, chunks of all segments
+  int steps;                // WH: 128-row steps of the problem
+  int g_m0[kWgXMaxGroups], g_m1[kWgXMaxGroups];   // X: M range of each group
+  int cbase[kMaxSeg + 1];   // SN: first chunk of each segment
+  size_t slab_bytes;        // fp32 partial sums this launch keeps in the workspace (0: it writes dW)
+};
+
+// Everything the host decides for one cvl_conv_wgrad[_grouped] call, computed once by wgrad_plan
+// (host only, the one reader of the family's cvl_dispatch_* / cvl_tune_* keys): one launch over all
+// groups, or one per group.  The launches run one after another on one workspace.
+struct WgradPlan {
+  int nlaunch;
+  WgLaunch l[kMaxSeg];
+  size_t workspace_bytes;
+};
+int wgrad_plan(const cvl_conv_desc* d, int ngroups, WgradPlan* p);
+
+// the descriptor a launch runs: its segments of the call's descriptor
+static inline cvl_conv_desc wgrad_launch_desc(const cvl_conv_desc* d, const WgLaunch& l) {
+  cvl_conv_desc s = *d;
+  s.nseg = l.nseg;
+  for (int i = 0; i < l.nseg; ++i) s.seg[i] = d->seg[l.seg0 + i];
+  return s;
+}
+
+// One launch group of cvl_conv_wgrad_batch: n problems in one WH or X launch with a common chunk, or
+// (kernel CVL_CK_NONE) one problem that runs as its own call with the plan `single`.
+struct WgBatchLaunch {
+  int kernel, tile;                 // CVL_CK_WG_H / CVL_CK_WG_X (tile 256 / 128) / CVL_CK_NONE
+  int n, idx[kWgXMaxProb];          // the problems, as indices into the call's list
+  int chunk;                        // rows (WH: steps) per workgroup, common to the group
+  int nsplit[kWgXMaxProb];
+  size_t slab_off[kWgXMaxProb];     // byte offset of each problem's slabs from ws_off
+  size_t ws_off, ws_bytes;          // the group's byte range in the workspace
+  WgradPlan single;
+};
+struct WgradBatchPlan {
+  std::vector<WgBatchLaunch> l;     // in launch order
+  size_t workspace_bytes;
+};
+int wgrad_batch_plan(const cvl_conv_desc* const* d, int n, WgradBatchPlan* p);
+
+// per-family predicates, next to the kernel geometry they test (a: the kWgSegM-padded layout of d)
+bool wg_sn_fits(const cvl_conv_desc* d, int ngroups);
+bool wg_h_fits(const cvl_conv_desc* d);
+bool wg_x_fits(const cvl_conv_desc* d, int ngroups, const ConvArgs& a);
+bool wg_x_batch_fits(const cvl_conv_desc* d, ConvArgs* a);
+bool wg_l_fits(const cvl_conv_desc* d, const ConvArgs& a);
+
+// the launchers: conv_wgrad{_sn,_h,_x,_l,}.hip.  d: the launch's own descriptor (wgrad_launch_desc), dw: its
+// groups' outputs, ws: the call's workspace.  They fill the kernel arguments and return the launch status.
+int launch_wg_sn(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                 void* ws, hipStream_t s);
+int launch_wg_h(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s);
+int launch_wg_x(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s);
+int launch_wg_l(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s);
+int launch_wg_s(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s);
+// the batched ones: problem i of the group is d[b.idx[i]] with x / dy / dw of the same index
+int launch_wg_x_batch(const WgBatchLaunch& b, const cvl_conv_desc* const* d, const void* const* x, const void* const* dy,
+                      float* const* dw, float beta, char* ws, hipStream_t s);
+int launch_wg_h_batch(const WgBatchLaunch& b, const cvl_conv_desc* const* d, const void* const* x, const void* const* dy,
+                      float* const* dw, float beta, char* ws, hipStream_t s);
+// a whole planned call (conv_wgrad.hip): its launches in order, last kernel set from the plan
+int wgrad_run(const WgradPlan& p, const cvl_conv_desc* d, const void* x, const void* dy, float* const* dw, float beta,
+              void* ws, hipStream_t s);
+
+// fp32 parity mode (parity_f32.hip)
+size_t cvl_conv_wgrad_f32_workspace(const cvl_conv_desc* d, int ngroups);
+int cvl_conv_wgrad_f32(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
+                       float beta, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 // destination row of GEMM row q (within image img) of segment S
 __device__ __forceinline__ long conv_dst_row(const ConvArgs& a, const ConvSeg& S, int img, int q) {

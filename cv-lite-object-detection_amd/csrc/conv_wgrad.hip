@@ -16,7 +16,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int BR = 64;     // reduction rows per step (two MFMA K-steps)
 constexpr int BKK = 128;   // k columns per tile
 constexpr int BM = 128;    // segment padding granule (must match conv_igemm)
 
@@ -259,165 +258,68 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
   }
 }
 
-int pick_splits(int tiles, int m_total, int bco) {
-  // 2 workgroups per CU at this kernel's occupancy (512 slots); modelled time = rounds x steps
-  // per workgroup (~0.8 us per 64-row step) + the fp32 slab round trip; the cheapest split wins
-  // rows per split at least: 128 (one BM granule) lets small-M launches (CenterNet 16x16 maps at
-  // bs 8: 2048 rows) spread over more workgroups: CenterNet 488 -> 510 img/s vs 512
-  const int min_chunk = cvl_tune_int("CVL_WG_MIN_CHUNK", 128);
-  int max_s = m_total / min_chunk;
-  if (max_s < 1) max_s = 1;
-  if (max_s > 8192 / tiles) max_s = 8192 / tiles > 1 ? 8192 / tiles : 1;
-  const double slab_us = (double)bco * BKK * 4 * 2 / 5.0e6;
-  int best = 1;
-  double best_t = 1e30;
-  for (int s = 1; s <= max_s; ++s) {
-    const int rounds = (tiles * s + 511) / 512;
-    const int steps = (m_total / s + BR - 1) / BR;
-    const double t = rounds * steps * 0.8 * bco / 128.0 + (s > 1 ? tiles * s * slab_us : 0.0);
-    if (t < best_t) { best_t = t; best = s; }
-  }
-  return best;
-}
-
 }  // namespace
 
-long cvl_conv_wgrad_l_workspace(const cvl_conv_desc* d);
-int cvl_conv_wgrad_l(const cvl_conv_desc* d, const void* x, const void* dy, float* dw, float beta,
-                     void* workspace, size_t workspace_bytes, hipStream_t s);
-
-long cvl_conv_wgrad_sn_workspace(const cvl_conv_desc* d, int ngroups);
-int cvl_conv_wgrad_sn(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
-                      float beta, void* workspace, size_t workspace_bytes, hipStream_t s);
-
-long cvl_conv_wgrad_x_workspace(const cvl_conv_desc* d, int ngroups);
-int cvl_conv_wgrad_x(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
-                     float beta, void* workspace, size_t workspace_bytes, hipStream_t s);
-
-namespace {
-
-// Single-group workspace of the L / 128-tile paths.
-size_t wgrad_single_workspace(const cvl_conv_desc* d) {
-  const long wl = cvl_conv_wgrad_l_workspace(d);     // the 128x256 LDS-DMA kernel takes the launch
-  if (wl >= 0) return (size_t)wl;
-  ConvArgs a;
-  if (cvl_conv_prepare(d, BM, &a)) return 0;
-  const int bco = a.Npad % 128 == 0 ? 128 : (a.Npad % 64 == 0 ? 64 : 32);
-  const int tiles = (a.Npad / bco) * ((a.K + BKK - 1) / BKK);
-  const int splits = pick_splits(tiles, a.m_total, bco);
-  return splits > 1 ? (size_t)splits * a.K * a.n_store * sizeof(float) : 16;
-}
-
-// Segments [g*nseg/ngroups, (g+1)*nseg/ngroups) of d as a descriptor of their own.
-cvl_conv_desc group_desc(const cvl_conv_desc* d, int ngroups, int gq) {
-  cvl_conv_desc s = *d;
-  const int spg = d->nseg / ngroups;
-  s.nseg = spg;
-  for (int i = 0; i < spg; ++i) s.seg[i] = d->seg[gq * spg + i];
-  return s;
-}
-
-int wgrad_single(const cvl_conv_desc* d, const void* x, const void* dy, float* dw, float beta, void* workspace,
-                 size_t workspace_bytes, hipStream_t s) {
-  {
-    float* dws[1] = {dw};
-    const int xst = cvl_conv_wgrad_x(d, 1, x, dy, dws, beta, workspace, workspace_bytes, s);
-    if (xst >= 0) return xst;
-  }
-  {
-    const int lst = cvl_conv_wgrad_l(d, x, dy, dw, beta, workspace, workspace_bytes, s);
-    if (lst >= 0) return lst;
-  }
+int launch_wg_s(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s) {
   WgArgs g;
-  int st = cvl_conv_prepare(d, BM, &g.a);
+  int st = cvl_conv_prepare(&d, BM, &g.a);
   if (st) return st;
   g.a.src = reinterpret_cast<const cvl_bf16*>(x);
   g.dy = reinterpret_cast<const cvl_bf16*>(dy);
-  g.ld_dy = d->ld_dst;
-  g.dy_coff = d->dst_coff;
-  g.Cout = d->n_store;
+  g.ld_dy = d.ld_dst;
+  g.dy_coff = d.dst_coff;
+  g.Cout = d.n_store;
   g.beta = beta;
-  const int bco = g.a.Npad % 128 == 0 ? 128 : (g.a.Npad % 64 == 0 ? 64 : 32);
-  g.co_tiles = g.a.Npad / bco;
-  g.k_tiles = (g.a.K + BKK - 1) / BKK;
-  const int tiles = g.co_tiles * g.k_tiles;
-  const int splits = pick_splits(tiles, g.a.m_total, bco);
-  int chunk = (g.a.m_total + splits - 1) / splits;
-  chunk = ((chunk + BM - 1) / BM) * BM;
-  const int nsplit = (g.a.m_total + chunk - 1) / chunk;
-  g.chunk = chunk;
-  g.direct = nsplit == 1;
-  if (!g.direct) {
-    CVL_CHECK_ARG(workspace && workspace_bytes >= (size_t)nsplit * g.a.K * g.Cout * sizeof(float));
-    g.out = reinterpret_cast<float*>(workspace);
-  } else {
-    g.out = dw;
-  }
-  dim3 grid(tiles, nsplit);
-  g_cvl_conv_last_kernel = CVL_CK_WG_S;
-  // 128-row steps (twice the MFMA work per barrier pair and loads in flight); the chunks are
-  // multiples of BM = 128, so a step never straddles a segment either way
-  const bool r128 = cvl_tune_flag("CVL_WG_BR128");
-  if (bco == 128) {
-    if (r128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, 64>), grid, dim3(NT), 0, s, g);
-  } else if (bco == 64) {
-    if (r128) hipLaunchKernelGGL((conv_wgrad_kernel<64, 128>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64>), grid, dim3(NT), 0, s, g);
-  } else {
-    if (r128) hipLaunchKernelGGL((conv_wgrad_kernel<32, 128>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<32, 64>), grid, dim3(NT), 0, s, g);
-  }
+  g.co_tiles = l.co_tiles;
+  g.k_tiles = l.tiles / l.co_tiles;
+  g.chunk = l.chunk;
+  g.direct = l.nsplit == 1;
+  g.out = g.direct ? dw[0] : reinterpret_cast<float*>(ws);
+  const dim3 grid(l.tiles, l.nsplit);
+  auto launch = [&](auto bco) {
+    constexpr int BCO = decltype(bco)::value;
+    if (l.rows == 128) hipLaunchKernelGGL((conv_wgrad_kernel<BCO, 128>), grid, dim3(NT), 0, s, g);
+    else hipLaunchKernelGGL((conv_wgrad_kernel<BCO, 64>), grid, dim3(NT), 0, s, g);
+  };
+  if (l.tile == 128) launch(std::integral_constant<int, 128>{});
+  else if (l.tile == 64) launch(std::integral_constant<int, 64>{});
+  else launch(std::integral_constant<int, 32>{});
   st = cvl_launch_status();
   if (st || g.direct) return st;
   const long n = (long)g.a.K * g.Cout;
-  const int blocks = (int)((n + 31) / 32);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s,
-                     (const float*)g.out, dw, n, nsplit, beta);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)((n + 31) / 32)), dim3(256), 0, s, (const float*)g.out, dw[0], n,
+                     l.nsplit, beta);
   return cvl_launch_status();
 }
 
-int check_wgrad_desc(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw) {
-  ConvArgs a;
-  int st = cvl_conv_prepare(d, BM, &a);
-  if (st) return st;
-  CVL_CHECK_ARG(d->mode == CVL_CONV_FWD && x && dy && dw);
-  CVL_CHECK_ARG(ngroups >= 1 && d->nseg % ngroups == 0);
-  CVL_CHECK_ARG(d->Cin % 8 == 0 && a.Npad % 32 == 0);
-  CVL_CHECK_ARG(d->ld_dst % 8 == 0 && d->dst_coff % 8 == 0 && d->ld_dst >= d->dst_coff + a.Npad);
-  const int spg = d->nseg / ngroups;
-  for (int gq = 0; gq < ngroups; ++gq) {
-    CVL_CHECK_ARG(dw[gq]);
-    for (int i = 1; i < spg; ++i) CVL_CHECK_ARG(d->seg[gq * spg + i].w == d->seg[gq * spg].w);  // shared weights
+// the launches of a planned call, one after another on the call's workspace
+int wgrad_run(const WgradPlan& p, const cvl_conv_desc* d, const void* x, const void* dy, float* const* dw, float beta,
+              void* ws, hipStream_t s) {
+  int group = 0;
+  for (int i = 0; i < p.nlaunch; ++i) {
+    const WgLaunch& l = p.l[i];
+    const cvl_conv_desc ld = wgrad_launch_desc(d, l);
+    g_cvl_conv_last_kernel = l.kernel;
+    int st;
+    switch (l.kernel) {
+      case CVL_CK_WG_SN: st = launch_wg_sn(l, ld, x, dy, dw + group, beta, ws, s); break;
+      case CVL_CK_WG_H: st = launch_wg_h(l, ld, x, dy, dw + group, beta, ws, s); break;
+      case CVL_CK_WG_X: st = launch_wg_x(l, ld, x, dy, dw + group, beta, ws, s); break;
+      case CVL_CK_WG_S: st = launch_wg_s(l, ld, x, dy, dw + group, beta, ws, s); break;
+      default: st = launch_wg_l(l, ld, x, dy, dw + group, beta, ws, s); break;
+    }
+    if (st) return st;
+    group += l.ngroups;
   }
   return CVL_OK;
 }
 
-}  // namespace
-
-long cvl_conv_wgrad_h_workspace(const cvl_conv_desc* d, int ngroups);
-int cvl_conv_wgrad_h(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw, float beta,
-                     void* workspace, size_t workspace_bytes, hipStream_t s);
-size_t cvl_conv_wgrad_f32_workspace(const cvl_conv_desc* d, int ngroups);
-int cvl_conv_wgrad_f32(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
-                       float beta, void* workspace, size_t workspace_bytes, hipStream_t s);
-
 extern "C" size_t cvl_conv_wgrad_grouped_workspace_size(const cvl_conv_desc* d, int ngroups) {
   if (!d || ngroups < 1 || d->nseg % ngroups) return 0;
   if (d->prec == CVL_PREC_F32) return cvl_conv_wgrad_f32_workspace(d, ngroups);
-  const long wsn = cvl_conv_wgrad_sn_workspace(d, ngroups);
-  if (wsn >= 0) return (size_t)(wsn > 16 ? wsn : 16);
-  const long wh = cvl_conv_wgrad_h_workspace(d, ngroups);
-  if (wh >= 0) return (size_t)wh;
-  const long wx = cvl_conv_wgrad_x_workspace(d, ngroups);
-  if (wx >= 0) return (size_t)wx;
-  size_t m = 16;
-  for (int gq = 0; gq < ngroups; ++gq) {      // the groups run one after another on one workspace
-    const cvl_conv_desc s = group_desc(d, ngroups, gq);
-    const size_t w = wgrad_single_workspace(&s);
-    m = w > m ? w : m;
-  }
-  return m;
+  WgradPlan p;
+  return wgrad_plan(d, ngroups, &p) ? 0 : p.workspace_bytes;
 }
 
 extern "C" size_t cvl_conv_wgrad_workspace_size(const cvl_conv_desc* d) {
@@ -428,32 +330,23 @@ extern "C" int cvl_conv_wgrad_grouped(const cvl_conv_desc* d, int ngroups, const
                                       float* const* dw, float beta, void* workspace, size_t workspace_bytes,
                                       cvl_stream_t stream) {
   CVL_CHECK_ARG(dw && d && ngroups >= 1);
-  // every writer of a dW with a pending deferred reduction (the split kernels below, but also the
-  // unsplit small-N / generic / fp32 paths that write dW directly) must see that reduction land
-  // first: flush here, before any path is chosen
+  hipStream_t s = (hipStream_t)stream;
+  // every writer of a dW with a pending deferred reduction (the split kernels, but also the unsplit
+  // paths that write dW directly) must see that reduction land first: flush here, before anything
+  // is planned or written
   for (int gq = 0; gq < ngroups; ++gq) {
-    const int gs = cvl_wgrad_defer_guard(dw[gq], (hipStream_t)stream);
+    const int gs = cvl_wgrad_defer_guard(dw[gq], s);
     if (gs) return gs;
   }
   if (d->prec == CVL_PREC_F32)                       // parity mode (parity_f32.hip)
-    return cvl_conv_wgrad_f32(d, ngroups, x, dy, dw, beta, workspace, workspace_bytes, (hipStream_t)stream);
-  CVL_CHECK_ARG(d->prec == CVL_PREC_BF16);
-  int st = check_wgrad_desc(d, ngroups, x, dy, dw);
+    return cvl_conv_wgrad_f32(d, ngroups, x, dy, dw, beta, workspace, workspace_bytes, s);
+  WgradPlan p;
+  const int st = wgrad_plan(d, ngroups, &p);
   if (st) return st;
-  hipStream_t s = (hipStream_t)stream;
-  const int snst = cvl_conv_wgrad_sn(d, ngroups, x, dy, dw, beta, workspace, workspace_bytes, s);
-  if (snst >= 0) return snst;
-  const int hst = cvl_conv_wgrad_h(d, ngroups, x, dy, dw, beta, workspace, workspace_bytes, s);
-  if (hst >= 0) return hst;
-  const int xst = cvl_conv_wgrad_x(d, ngroups, x, dy, dw, beta, workspace, workspace_bytes, s);
-  if (xst >= 0) return xst;
-  if (ngroups == 1) return wgrad_single(d, x, dy, dw[0], beta, workspace, workspace_bytes, s);
-  for (int gq = 0; gq < ngroups; ++gq) {
-    const cvl_conv_desc sd = group_desc(d, ngroups, gq);
-    st = wgrad_single(&sd, x, dy, dw[gq], beta, workspace, workspace_bytes, s);
-    if (st) return st;
-  }
-  return CVL_OK;
+  CVL_CHECK_ARG(x && dy && workspace && workspace_bytes >= p.workspace_bytes);
+  for (int i = 0; i < p.nlaunch; ++i) CVL_CHECK_ARG(p.l[i].slab_bytes <= workspace_bytes);
+  for (int gq = 0; gq < ngroups; ++gq) CVL_CHECK_ARG(dw[gq]);
+  return wgrad_run(p, d, x, dy, dw, beta, workspace, s);
 }
 
 extern "C" int cvl_conv_wgrad(const cvl_conv_desc* d, const void* x, const void* dy, float* dw,
@@ -461,4 +354,41 @@ extern "C" int cvl_conv_wgrad(const cvl_conv_desc* d, const void* x, const void*
                               cvl_stream_t stream) {
   float* dws[1] = {dw};
   return cvl_conv_wgrad_grouped(d, 1, x, dy, dws, beta, workspace, workspace_bytes, stream);
+}
+
+// ---- cvl_conv_wgrad_batch ---------------------------------------------------------------------------
+extern "C" size_t cvl_conv_wgrad_batch_workspace_size(const cvl_conv_desc* const* d, int n) {
+  WgradBatchPlan p;
+  return wgrad_batch_plan(d, n, &p) ? 16 : p.workspace_bytes;
+}
+
+extern "C" int cvl_conv_wgrad_batch(const cvl_conv_desc* const* d, int n, const void* const* x, const void* const* dy,
+                                    float* const* dw, float beta, void* workspace, size_t workspace_bytes,
+                                    cvl_stream_t stream) {
+  CVL_CHECK_ARG(d && x && dy && dw && n >= 1);
+  for (int i = 0; i < n; ++i) {
+    CVL_CHECK_ARG(d[i] && x[i] && dy[i] && dw[i]);
+    for (int j = 0; j < i; ++j) CVL_CHECK_ARG(dw[j] != dw[i]);
+  }
+  WgradBatchPlan p;
+  int st = wgrad_batch_plan(d, n, &p);
+  if (st) return st;
+  CVL_CHECK_ARG(workspace && workspace_bytes >= p.workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < n; ++i) {                   // a pending reduction into one of these dW lands first
+    const int gs = cvl_wgrad_defer_guard(dw[i], s);
+    if (gs) return gs;
+  }
+  for (const WgBatchLaunch& b : p.l) {
+    char* ws = reinterpret_cast<char*>(workspace) + b.ws_off;
+    const int i0 = b.idx[0];
+    if (b.kernel != CVL_CK_NONE) g_cvl_conv_last_kernel = b.kernel;
+    if (b.kernel == CVL_CK_WG_H) st = launch_wg_h_batch(b, d, x, dy, dw, beta, ws, s);
+    else if (b.kernel == CVL_CK_WG_X) st = launch_wg_x_batch(b, d, x, dy, dw, beta, ws, s);
+    else if (d[i0]->prec == CVL_PREC_F32)         // a problem neither batched kernel takes: as its own call
+      st = cvl_conv_wgrad_f32(d[i0], 1, x[i0], dy[i0], dw + i0, beta, ws, b.single.workspace_bytes, s);
+    else st = wgrad_run(b.single, d[i0], x[i0], dy[i0], dw + i0, beta, ws, s);
+    if (st) return st;
+  }
+  return CVL_OK;
 }

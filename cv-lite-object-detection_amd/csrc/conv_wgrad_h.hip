@@ -31,7 +31,6 @@ constexpr int HPW = HPX / 8 / 8;                     // halo DMA pieces (8 pixel
 constexpr int HALO_B = HPX * 128;                    // bytes
 constexpr int DY_B = RS * 128;
 constexpr int STAGE_B = HALO_B + DY_B;               // 73,728 B
-constexpr unsigned kRecords = 0x7fffffffu;
 constexpr unsigned kOOB = 0x80000000u;
 
 __device__ __forceinline__ int swz8(int p) { return ((((p >> 1) & 1) | (((p >> 3) & 1) << 1)) << 1); }
@@ -55,7 +54,7 @@ struct WhArgs {
 // Batched form (round 6, cvl_conv_wgrad_batch): the 3x3 weight gradients of a ResNet stage's
 // units in ONE launch; workgroup L (after the XCD remap) works on the problem whose [wg0, wg0 +
 // tiles * nsplit) range holds it, with that problem's own arguments.
-constexpr int kMaxWhProb = 12;
+constexpr int kMaxWhProb = kWgHMaxProb;
 struct WhBatch {
   WhArgs p[kMaxWhProb];
   int wg0[kMaxWhProb];
@@ -111,8 +110,8 @@ __global__ void __launch_bounds__(NT) conv_wgrad_h_kernel(Args ga) {
     const int m = 8 * (wave + 8 * j) + (lane >> 3);
     ylo[j] = (unsigned)((m * g.ld_dy + g.dy_coff + co0) * 2) + (unsigned)((ch ^ swz8(m)) * 16);
   }
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, (short)0, (int)kRecords, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)g.dy, (short)0, (int)kRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, (short)0, (int)kConvBufRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)g.dy, (short)0, (int)kConvBufRecords, 0x00020000);
 
   auto issue = [&](int s) {
     if (s >= s1) return;
@@ -245,13 +244,25 @@ __global__ void __launch_bounds__(NT) conv_wgrad_h_kernel(Args ga) {
 }
 
 
-struct WhPlan {
-  int steps, nsplit, chunk;
-  size_t slab;
-};
+// one problem's kernel arguments but the pointers and beta: its 128-row steps in chunks of `chunk`
+void wh_args(const cvl_conv_desc& d, int chunk, int nsplit, WhArgs* g) {
+  const cvl_conv_seg& q = d.seg[0];
+  g->src_base = q.src_base; g->src_img = q.src_img; g->dst_base = q.dst_base; g->dst_img = q.dst_img;
+  g->B = d.B; g->H = q.Hr; g->W = q.Wr; g->Cin = d.Cin; g->Cout = d.n_store;
+  g->ld_dy = d.ld_dst; g->dy_coff = d.dst_coff;
+  g->ci_tiles = d.Cin / BCI; g->co_tiles = d.n_store / BCO;
+  g->steps = d.B * q.Hr * q.Wr / RS;
+  g->chunk = chunk; g->nsplit = nsplit;
+  g->direct = nsplit == 1;
+}
 
-inline bool wh_plan(const cvl_conv_desc* d, int ngroups, WhPlan* pl) {
-  if (cvl_dispatch_flag("wg_no_h") || ngroups != 1 || d->nseg != 1 || d->mode != CVL_CONV_FWD) return false;
+}  // namespace
+
+// What the halo kernel can run: bf16, 3x3 / stride 1 / pad 1, one dense segment of whole 128-row
+// steps (map width 16 .. 128 dividing 128), 64-channel tiles on both sides, a halo that fits its
+// LDS stage, 32-bit buffer offsets.
+bool wg_h_fits(const cvl_conv_desc* d) {
+  if (d->nseg != 1 || d->mode != CVL_CONV_FWD) return false;
   if (d->prec != CVL_PREC_BF16 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 ||
       d->relu_in || d->Cin % BCI || d->n_store % BCO || d->ld_dst % 8 || d->dst_coff % 8)
     return false;
@@ -261,157 +272,50 @@ inline bool wh_plan(const cvl_conv_desc* d, int ngroups, WhPlan* pl) {
   if ((RS / W + 2) * ((W + 2 + 15) & ~15) > HPX) return false;
   const long src_end = (q.src_base + (long)d->B * q.src_img) * d->Cin * 2;
   const long dy_end = (q.dst_base + (long)d->B * q.dst_img) * d->ld_dst * 2;
-  if (src_end >= (long)kRecords - 65536 || dy_end >= (long)kRecords - 65536) return false;
-  const int tiles = (d->Cin / BCI) * (d->n_store / BCO);
-  pl->steps = d->B * HW / RS;
-  // one workgroup per CU (134 KiB of LDS): ~256 workgroups, >= 4 steps each
-  const int target = cvl_tune_int("CVL_WGH_WGS", 256);
-  int ns = (target + tiles - 1) / tiles;
-  if (ns > pl->steps / 4) ns = pl->steps / 4;
-  if (ns < 1) ns = 1;
-  pl->chunk = (pl->steps + ns - 1) / ns;
-  pl->nsplit = (pl->steps + pl->chunk - 1) / pl->chunk;
-  pl->slab = pl->nsplit > 1 ? (size_t)pl->nsplit * 9 * d->Cin * d->n_store * sizeof(float) : 0;
-  return true;
+  return src_end < (long)kConvBufRecords - 65536 && dy_end < (long)kConvBufRecords - 65536;
 }
 
-}  // namespace
-
-// workspace the halo weight gradient needs (>= 16), or -1 when the launch does not qualify
-long cvl_conv_wgrad_h_workspace(const cvl_conv_desc* d, int ngroups) {
-  WhPlan pl;
-  if (!d || !wh_plan(d, ngroups, &pl)) return -1;
-  return (long)(pl.slab > 16 ? pl.slab : 16);
-}
-
-int cvl_conv_wgrad_h(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw, float beta,
-                     void* workspace, size_t workspace_bytes, hipStream_t s) {
-  WhPlan pl;
-  if (!wh_plan(d, ngroups, &pl)) return -1;
-  if (!workspace || workspace_bytes < (pl.slab > 16 ? pl.slab : 16)) return CVL_EINVAL;
-  const cvl_conv_seg& q = d->seg[0];
+int launch_wg_h(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s) {
   WhArgs g;
+  wh_args(d, l.chunk, l.nsplit, &g);
   g.x = reinterpret_cast<const cvl_bf16*>(x);
   g.dy = reinterpret_cast<const cvl_bf16*>(dy);
-  g.src_base = q.src_base; g.src_img = q.src_img; g.dst_base = q.dst_base; g.dst_img = q.dst_img;
-  g.B = d->B; g.H = q.Hr; g.W = q.Wr; g.Cin = d->Cin; g.Cout = d->n_store;
-  g.ld_dy = d->ld_dst; g.dy_coff = d->dst_coff;
-  g.ci_tiles = d->Cin / BCI; g.co_tiles = d->n_store / BCO;
-  g.steps = pl.steps; g.chunk = pl.chunk; g.nsplit = pl.nsplit;
-  g.direct = pl.nsplit == 1;
   g.beta = beta;
-  g.out = g.direct ? dw[0] : reinterpret_cast<float*>(workspace);
-  g_cvl_conv_last_kernel = CVL_CK_WG_H;
-  if (g.direct) {                               // writes dW now: a queued reduction into it first
-    const int gs = cvl_wgrad_defer_guard(dw[0], s);
-    if (gs) return gs;
-  }
-  hipLaunchKernelGGL(conv_wgrad_h_kernel<WhArgs>, dim3(g.ci_tiles * g.co_tiles * pl.nsplit), dim3(NT), 0, s, g);
-  int st = cvl_launch_status();
+  g.out = g.direct ? dw[0] : reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(conv_wgrad_h_kernel<WhArgs>, dim3(g.ci_tiles * g.co_tiles * l.nsplit), dim3(NT), 0, s, g);
+  const int st = cvl_launch_status();
   if (st || g.direct) return st;
-  return cvl_wgrad_reduce((const float*)workspace, dw[0], dw[0], 9L * d->Cin * d->n_store / 4, pl.nsplit, 1, beta, s);
+  return cvl_wgrad_reduce((const float*)ws, dw[0], dw[0], 9L * d.Cin * d.n_store / 4, l.nsplit, 1, beta, s);
 }
 
-// ---- batched 3x3 weight gradients (cvl_conv_wgrad_batch) --------------------------------------------
-// problems wh_plan takes; a common chunk (128-row steps per workgroup) for the launch from the cost
-// model rounds x (fixed + chunk x step) + slab round trips (defaults: CVL_WGHB_FIX / _STEP, us x 100)
-bool cvl_wgrad_h_batch_ok(const cvl_conv_desc* d) {
-  WhPlan pl;
-  return d && wh_plan(d, 1, &pl);
-}
-
-int cvl_wgrad_h_batch_max() { return kMaxWhProb; }
-
-namespace {
-struct WhBatchPlan {
-  WhBatch b;
-  size_t slab_off[kMaxWhProb];
-  size_t bytes;
-  int wgs;
-};
-
-void wh_batch_plan(const cvl_conv_desc* const* d, const int* idx, int n, WhBatchPlan* pl) {
-  int tiles[kMaxWhProb], steps[kMaxWhProb], maxs = 1;
-  for (int i = 0; i < n; ++i) {
-    const cvl_conv_desc* q = d[idx[i]];
-    tiles[i] = (q->Cin / BCI) * (q->n_store / BCO);
-    steps[i] = q->B * q->seg[0].Hr * q->seg[0].Wr / RS;
-    maxs = steps[i] > maxs ? steps[i] : maxs;
-  }
-  static const int ncu = cvl_device_cus();
-  const double fix = cvl_tune_int("CVL_WGHB_FIX", 800) / 100.0, step = cvl_tune_int("CVL_WGHB_STEP", 300) / 100.0;
-  const double slab_us = (double)9 * BCI * BCO * 4 * 2 / 5.0e6;
-  int best_c = maxs;
-  double best_t = 1e30;
-  for (int c = 1;; c *= 2) {
-    const int cc = c < maxs ? c : maxs;
-    long w = 0, sl = 0;
-    for (int i = 0; i < n; ++i) {
-      const int sp = (steps[i] + cc - 1) / cc;
-      w += (long)tiles[i] * sp;
-      if (sp > 1) sl += (long)tiles[i] * sp;
-    }
-    const double t = (double)((w + ncu - 1) / ncu) * (fix + cc * step) + sl * slab_us;
-    if (t < best_t) {
-      best_t = t;
-      best_c = cc;
-    }
-    if (cc >= maxs) break;
-  }
-  const int forced = cvl_tune_int("CVL_WGHB_CHUNK", 0);
-  if (forced > 0) best_c = forced;
-  size_t off = 0;
+// the 3x3 weight gradients of a ResNet stage's units in one launch, each problem in chunks of at
+// most the group's common chunk
+int launch_wg_h_batch(const WgBatchLaunch& b, const cvl_conv_desc* const* d, const void* const* x, const void* const* dy,
+                      float* const* dw, float beta, char* ws, hipStream_t s) {
+  static_assert(kMaxWhProb <= kWgXMaxProb, "WgBatchLaunch holds every problem of a launch");
+  WhBatch a;
   int wg = 0;
-  for (int i = 0; i < n; ++i) {
-    const cvl_conv_desc* q = d[idx[i]];
-    const cvl_conv_seg& sq = q->seg[0];
-    WhArgs& g = pl->b.p[i];
-    g.src_base = sq.src_base; g.src_img = sq.src_img; g.dst_base = sq.dst_base; g.dst_img = sq.dst_img;
-    g.B = q->B; g.H = sq.Hr; g.W = sq.Wr; g.Cin = q->Cin; g.Cout = q->n_store;
-    g.ld_dy = q->ld_dst; g.dy_coff = q->dst_coff;
-    g.ci_tiles = q->Cin / BCI; g.co_tiles = q->n_store / BCO;
-    g.steps = steps[i];
-    g.chunk = best_c < steps[i] ? best_c : steps[i];
-    g.nsplit = (steps[i] + g.chunk - 1) / g.chunk;
-    g.direct = g.nsplit == 1;
-    pl->b.wg0[i] = wg;
-    wg += tiles[i] * g.nsplit;
-    pl->slab_off[i] = off;
-    if (!g.direct) off += ((size_t)g.nsplit * 9 * q->Cin * q->n_store * sizeof(float) + 255) & ~(size_t)255;
-  }
-  for (int i = n; i < kMaxWhProb; ++i) pl->b.wg0[i] = 0x7fffffff;
-  pl->b.n = n;
-  pl->bytes = off;
-  pl->wgs = wg;
-}
-}  // namespace
-
-size_t cvl_wgrad_h_batch_workspace(const cvl_conv_desc* const* d, const int* idx, int n) {
-  WhBatchPlan pl;
-  wh_batch_plan(d, idx, n, &pl);
-  return pl.bytes;
-}
-
-// n problems (all cvl_wgrad_h_batch_ok) in one launch; slabs in workspace (>= the size above)
-int cvl_wgrad_h_batch(const cvl_conv_desc* const* d, const int* idx, int n, const void* const* x, const void* const* dy,
-                      float* const* dw, float beta, void* workspace, hipStream_t s) {
-  WhBatchPlan pl;
-  wh_batch_plan(d, idx, n, &pl);
-  char* ws = reinterpret_cast<char*>(workspace);
-  for (int i = 0; i < n; ++i) {
-    WhArgs& g = pl.b.p[i];
-    g.x = reinterpret_cast<const cvl_bf16*>(x[idx[i]]);
-    g.dy = reinterpret_cast<const cvl_bf16*>(dy[idx[i]]);
-    g.out = g.direct ? dw[idx[i]] : reinterpret_cast<float*>(ws + pl.slab_off[i]);
+  for (int i = 0; i < kMaxWhProb; ++i) {
+    a.wg0[i] = 0x7fffffff;
+    if (i >= b.n) continue;
+    const int pi = b.idx[i];
+    WhArgs& g = a.p[i];
+    const int steps = d[pi]->B * d[pi]->seg[0].Hr * d[pi]->seg[0].Wr / RS;
+    wh_args(*d[pi], b.chunk < steps ? b.chunk : steps, b.nsplit[i], &g);
+    g.x = reinterpret_cast<const cvl_bf16*>(x[pi]);
+    g.dy = reinterpret_cast<const cvl_bf16*>(dy[pi]);
+    g.out = g.direct ? dw[pi] : reinterpret_cast<float*>(ws + b.slab_off[i]);
     g.beta = beta;
+    a.wg0[i] = wg;
+    wg += g.ci_tiles * g.co_tiles * g.nsplit;
   }
-  g_cvl_conv_last_kernel = CVL_CK_WG_H;
-  hipLaunchKernelGGL(conv_wgrad_h_kernel<WhBatch>, dim3(pl.wgs), dim3(NT), 0, s, pl.b);
+  a.n = b.n;
+  hipLaunchKernelGGL(conv_wgrad_h_kernel<WhBatch>, dim3(wg), dim3(NT), 0, s, a);
   int st = cvl_launch_status();
-  for (int i = 0; !st && i < n; ++i) {
-    const WhArgs& g = pl.b.p[i];
-    if (g.direct) continue;
-    st = cvl_wgrad_reduce(g.out, dw[idx[i]], dw[idx[i]], 9L * g.Cin * g.Cout / 4, g.nsplit, 1, beta, s);
+  for (int i = 0; !st && i < b.n; ++i) {
+    const WhArgs& g = a.p[i];
+    if (!g.direct) st = cvl_wgrad_reduce(g.out, dw[b.idx[i]], dw[b.idx[i]], 9L * g.Cin * g.Cout / 4, g.nsplit, 1, beta, s);
   }
   return st;
 }

@@ -282,97 +282,37 @@ __global__ void wgrad_l_reduce_kernel(const float* slab, float* dw, long n4, int
   }
 }
 
-// One workgroup per CU (134-150 KiB LDS).  Modelled time of (tile width, split count s): rounds of
-// 256 workgroups x 64-row blocks per workgroup (measured on the FCOS P3 tower shape: ~2.8 us per
-// block at the 128-wide co tile, ~4.4 us at the 256-wide one) + the fp32 slab round trip (write +
-// read at ~5 TB/s); the cheapest plan wins.
-inline double wl_time(int tiles, int m_total, int bco, int* best_s) {
-  int max_s = m_total / 512;
-  if (max_s < 1) max_s = 1;
-  if (max_s > 4096 / tiles) max_s = 4096 / tiles > 1 ? 4096 / tiles : 1;
-  // sweep knobs (tools/gpu_knob_sweep.sh): slab cost in percent, block times in 0.1 us
-  const double slab_us = (double)bco * BKK * 4 * 2 / 5.0e6 * cvl_tune_int("CVL_WGL_SLAB_PCT", 100) / 100.0;
-  const double blk_us = bco == 256 ? cvl_tune_int("CVL_WGL_BLK256", 44) / 10.0 : cvl_tune_int("CVL_WGL_BLK128", 28) / 10.0;
-  double best_t = 1e30;
-  *best_s = 1;
-  for (int s = 1; s <= max_s; ++s) {
-    const int rounds = (tiles * s + 255) / 256;
-    const int blocks = (m_total / s + 63) / 64;
-    const double t = rounds * blocks * blk_us + (s > 1 ? tiles * s * slab_us : 0.0);
-    if (t < best_t) { best_t = t; *best_s = s; }
-  }
-  return best_t;
-}
-
-// Npad 128 (one 128-wide co tile) runs faster on the register-staged 128 x 128 kernel
-// (tools/wgrad_sweep.py at bs 16: 3x3 128->128 @ 64x64 85 -> 72 us, 1x1 512->128 65 -> 46 us)
-inline bool wl_eligible(const cvl_conv_desc* d, const ConvArgs& a) {
-  return !cvl_dispatch_flag("wg_no_l") && !d->relu_in && a.K >= BKK && d->Cin % 8 == 0 &&
-         d->n_store % 4 == 0 && a.m_total >= 1024 && a.Npad % 128 == 0 &&
-         a.Npad >= cvl_tune_int("CVL_WGL_MIN_NPAD", 256);
-}
-
-struct WlPlan {
-  int bco, tiles, chunk, nsplit;
-  size_t slab, total;
-};
-
-inline bool wl_plan(const cvl_conv_desc* d, ConvArgs* a, WlPlan* p) {
-  if (cvl_conv_prepare(d, SEGM, a) || !wl_eligible(d, *a)) return false;
-  const int kt = (a->K + BKK - 1) / BKK;
-  int s128 = 1, s256 = 1;
-  const double t128 = wl_time((a->Npad / 128) * kt, a->m_total, 128, &s128);
-  double t256 = 1e30;
-  if (a->Npad % 256 == 0 && !cvl_tune_flag("CVL_WGRAD_NO_256"))
-    t256 = wl_time((a->Npad / 256) * kt, a->m_total, 256, &s256);
-  p->bco = t256 < t128 ? 256 : 128;
-  p->tiles = (a->Npad / p->bco) * kt;
-  const int splits = p->bco == 256 ? s256 : s128;
-  const int chunk = (a->m_total + splits - 1) / splits;
-  p->chunk = ((chunk + SEGM - 1) / SEGM) * SEGM;
-  p->nsplit = (a->m_total + p->chunk - 1) / p->chunk;
-  p->slab = p->nsplit > 1 ? (size_t)p->nsplit * a->K * d->n_store * sizeof(float) : 0;
-  p->total = p->slab > 0 ? p->slab : 16;
-  return true;
-}
-
 }  // namespace
 
-// Workspace the large-tile path needs, or -1 when the launch does not qualify.
-long cvl_conv_wgrad_l_workspace(const cvl_conv_desc* d) {
-  ConvArgs a;
-  WlPlan p;
-  if (!wl_plan(d, &a, &p)) return -1;
-  return (long)p.total;
+// What the large-tile kernel can run: no ReLU on the source, K of at least one 256-deep tile, whole
+// 128-wide co tiles, 16-B source pieces, 4-float output pieces, at least 1024 rows.
+bool wg_l_fits(const cvl_conv_desc* d, const ConvArgs& a) {
+  return !d->relu_in && a.K >= BKK && d->Cin % 8 == 0 && d->n_store % 4 == 0 && a.m_total >= 1024 && a.Npad % 128 == 0;
 }
 
-// Returns -1 when the launch does not qualify (caller uses the 128x128 kernel), else a status.
-int cvl_conv_wgrad_l(const cvl_conv_desc* d, const void* x, const void* dy, float* dw, float beta,
-                     void* workspace, size_t workspace_bytes, hipStream_t s) {
+int launch_wg_l(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s) {
   WgLArgs g;
-  WlPlan p;
-  if (!wl_plan(d, &g.a, &p)) return -1;
-  if (!workspace || workspace_bytes < p.total) return CVL_EINVAL;
+  int st = cvl_conv_prepare(&d, SEGM, &g.a);
+  if (st) return st;
   g.a.src = reinterpret_cast<const cvl_bf16*>(x);
   g.dy = reinterpret_cast<const cvl_bf16*>(dy);
-  g.ld_dy = d->ld_dst;
-  g.dy_coff = d->dst_coff;
-  g.Cout = d->n_store;
+  g.ld_dy = d.ld_dst;
+  g.dy_coff = d.dst_coff;
+  g.Cout = d.n_store;
   g.beta = beta;
-  g.co_tiles = g.a.Npad / p.bco;
-  g.chunk = p.chunk;
-  g.nsplit = p.nsplit;
-  g.direct = p.nsplit == 1;
-  g.out = g.direct ? dw : reinterpret_cast<float*>(workspace);
-  g_cvl_conv_last_kernel = p.bco == 256 ? CVL_CK_WG_L256 : CVL_CK_WG_L128;
-  if (p.bco == 256) hipLaunchKernelGGL(conv_wgrad_l_kernel<256>, dim3(p.tiles * p.nsplit), dim3(NT), 0, s, g);
-  else hipLaunchKernelGGL(conv_wgrad_l_kernel<128>, dim3(p.tiles * p.nsplit), dim3(NT), 0, s, g);
-  int st = cvl_launch_status();
+  g.co_tiles = l.co_tiles;
+  g.chunk = l.chunk;
+  g.nsplit = l.nsplit;
+  g.direct = l.nsplit == 1;
+  g.out = g.direct ? dw[0] : reinterpret_cast<float*>(ws);
+  if (l.tile == 256) hipLaunchKernelGGL(conv_wgrad_l_kernel<256>, dim3(l.tiles * l.nsplit), dim3(NT), 0, s, g);
+  else hipLaunchKernelGGL(conv_wgrad_l_kernel<128>, dim3(l.tiles * l.nsplit), dim3(NT), 0, s, g);
+  st = cvl_launch_status();
   if (st || g.direct) return st;
   const long n4 = (long)g.a.K * g.Cout / 4;
   int blocks = (int)((n4 + 255) / 256);
   blocks = blocks > 4096 ? 4096 : blocks;
-  hipLaunchKernelGGL(wgrad_l_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)g.out, dw, n4, p.nsplit,
-                     beta);
+  hipLaunchKernelGGL(wgrad_l_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)g.out, dw[0], n4, l.nsplit, beta);
   return cvl_launch_status();
 }

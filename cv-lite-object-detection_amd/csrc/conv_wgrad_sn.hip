@@ -33,7 +33,6 @@ constexpr int CI = 128;         // input channels per workgroup
 constexpr int NP = 32;          // output columns per tap (Npad)
 constexpr int MAXT = 9;         // taps (KH*KW <= 9)
 constexpr int NSLOT = 3;
-constexpr unsigned kRecords = 0x7fffffffu;
 constexpr unsigned kOOB = 0x80000000u;
 #ifndef CVL_SN_ABL
 #define CVL_SN_ABL 0            // measurement variants only: 1 no DMA, 2 no fragment reads, 4 no MFMAs, 8 no stores, 16 no loop
@@ -143,8 +142,8 @@ __global__ void __launch_bounds__(NT) conv_wgrad_sn_kernel(SnArgs g) {
     yp[j] = pos_of(lo + rr);
     ycol[j] = (unsigned)((g.dy_coff + ((lane & 3) ^ yswz(rr)) * 8) * 2);
   }
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, (short)0, (int)kRecords, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)g.dy, (short)0, (int)kRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)g.x, (short)0, (int)kConvBufRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)g.dy, (short)0, (int)kConvBufRecords, 0x00020000);
   const bool yfull = wave < C::YW;        // issues YJ dY instructions (else YJ - 1)
   auto issue = [&](int slot) {
     const char* base = lds + slot * C::SLOTB;
@@ -296,100 +295,57 @@ __global__ void __launch_bounds__(256) wgrad_sn_reduce_kernel(SnReduce r) {
   *o = s;
 }
 
-struct SnPlan {
-  int CH, nch, ci_tiles, T;
-  int cbase[kMaxSeg + 1];
-  size_t slab;
-};
+}  // namespace
 
-bool sn_plan(const cvl_conv_desc* d, int ngroups, SnPlan* p) {
-  if (cvl_tune_flag("CVL_WGRAD_NO_SN")) return false;
-  if (!d || d->mode != CVL_CONV_FWD || d->stride != 1 || d->Npad != NP || d->relu_in) return false;
-  if (d->Cin % CI || d->KH * d->KW > MAXT || d->nseg < 1 || d->nseg > kMaxSeg || ngroups < 1 ||
+// What the small-N kernel can run: stride 1 "same" convs of 1 or 9 taps with Npad 32 and whole
+// 128-channel input tiles, no ReLU on the source, 16-B dY rows, 32-bit buffer offsets (the DMA's voffset).
+bool wg_sn_fits(const cvl_conv_desc* d, int ngroups) {
+  if (d->mode != CVL_CONV_FWD || d->stride != 1 || d->Npad != NP || d->relu_in) return false;
+  if (d->Cin % CI || (d->KH * d->KW != 1 && d->KH * d->KW != MAXT) || d->nseg < 1 || d->nseg > kMaxSeg || ngroups < 1 ||
       d->nseg % ngroups)
     return false;
   if (d->ld_dst % 8 || d->dst_coff % 8 || d->ld_dst < d->dst_coff + NP) return false;
-  long rows = 0;
   for (int i = 0; i < d->nseg; ++i) {
     const cvl_conv_seg& s = d->seg[i];
     if (s.Hr != s.Hs || s.Wr != s.Ws) return false;     // "same" geometry: dY and x share the map
-    rows += (long)d->B * s.Hr * s.Wr;
-  }
-  // 32-bit buffer offsets (the DMA's voffset)
-  for (int i = 0; i < d->nseg; ++i) {
-    const cvl_conv_seg& s = d->seg[i];
     const long simg = s.src_img ? s.src_img : (long)s.Hs * s.Ws, dimg = s.dst_img ? s.dst_img : (long)s.Hr * s.Wr;
     if ((s.src_base + d->B * simg) * d->Cin * 2 >= (1l << 31) || (s.dst_base + d->B * dimg) * d->ld_dst * 2 >= (1l << 31))
       return false;
   }
-  p->T = d->KH * d->KW;
-  p->ci_tiles = d->Cin / CI;
-  // ~256 workgroups (one per CU: the 156-KiB LDS ring); chunk = whole steps
-  static const int wgs = cvl_tune_int("CVL_SN_WGS", 256);
-  const long want = wgs / p->ci_tiles;
-  long ch = (rows + want - 1) / want;
-  ch = ((ch + BR - 1) / BR) * BR;
-  if (ch < 4 * BR) ch = 4 * BR;
-  p->CH = (int)ch;
-  int c = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    p->cbase[i] = c;
-    const long r = (long)d->B * d->seg[i].Hr * d->seg[i].Wr;
-    c += (int)((r + ch - 1) / ch);
-  }
-  p->cbase[d->nseg] = c;
-  p->nch = c;
-  p->slab = (size_t)c * p->T * d->Cin * ((d->n_store + 3) & ~3) * sizeof(float);
   return true;
 }
 
-}  // namespace
-
-long cvl_conv_wgrad_sn_workspace(const cvl_conv_desc* d, int ngroups) {
-  SnPlan p;
-  if (!sn_plan(d, ngroups, &p)) return -1;
-  return (long)p.slab;
-}
-
-// Returns -1 when the launch does not qualify (the caller takes another kernel), else a status.
-int cvl_conv_wgrad_sn(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
-                      float beta, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  SnPlan p;
-  if (!sn_plan(d, ngroups, &p)) return -1;
-  if (!workspace || workspace_bytes < p.slab) return CVL_EINVAL;
+int launch_wg_sn(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                 void* ws, hipStream_t s) {
   SnArgs g;
   g.x = reinterpret_cast<const cvl_bf16*>(x);
   g.dy = reinterpret_cast<const cvl_bf16*>(dy);
-  g.slab = reinterpret_cast<float*>(workspace);
-  g.Cin = d->Cin; g.KH = d->KH; g.KW = d->KW; g.T = p.T; g.pad_t = d->pad_t; g.pad_l = d->pad_l;
-  g.ld_dy = d->ld_dst; g.dy_coff = d->dst_coff; g.nseg = d->nseg; g.B = d->B; g.CH = p.CH;
-  g.ci_tiles = p.ci_tiles;
-  g.nw = (d->n_store + 3) & ~3;
-  for (int i = 0; i <= kMaxSeg; ++i) g.cbase[i] = i <= d->nseg ? p.cbase[i] : p.nch;
+  g.slab = reinterpret_cast<float*>(ws);
+  g.Cin = d.Cin; g.KH = d.KH; g.KW = d.KW; g.T = d.KH * d.KW; g.pad_t = d.pad_t; g.pad_l = d.pad_l;
+  g.ld_dy = d.ld_dst; g.dy_coff = d.dst_coff; g.nseg = d.nseg; g.B = d.B; g.CH = l.chunk;
+  g.ci_tiles = l.tiles;
+  g.nw = (d.n_store + 3) & ~3;
+  for (int i = 0; i <= kMaxSeg; ++i) g.cbase[i] = l.cbase[i];
   for (int i = 0; i < kMaxSeg; ++i) {
-    const cvl_conv_seg& q = d->seg[i < d->nseg ? i : 0];
+    const cvl_conv_seg& q = d.seg[i < d.nseg ? i : 0];
     g.H[i] = q.Hs; g.W[i] = q.Ws;
     g.src_base[i] = q.src_base; g.src_img[i] = q.src_img ? q.src_img : (long)q.Hs * q.Ws;
     g.dst_base[i] = q.dst_base; g.dst_img[i] = q.dst_img ? q.dst_img : (long)q.Hr * q.Wr;
   }
-  g_cvl_conv_last_kernel = CVL_CK_WG_SN;
-  const dim3 grid(p.ci_tiles * p.nch);
-  switch (p.T) {
-    case 9: hipLaunchKernelGGL(conv_wgrad_sn_kernel<9>, grid, dim3(NT), 0, s, g); break;
-    case 1: hipLaunchKernelGGL(conv_wgrad_sn_kernel<1>, grid, dim3(NT), 0, s, g); break;
-    default: return -1;
-  }
-  int st = cvl_launch_status();
+  const dim3 grid(l.tiles * l.nsplit);
+  if (g.T == MAXT) hipLaunchKernelGGL(conv_wgrad_sn_kernel<9>, grid, dim3(NT), 0, s, g);
+  else hipLaunchKernelGGL(conv_wgrad_sn_kernel<1>, grid, dim3(NT), 0, s, g);
+  const int st = cvl_launch_status();
   if (st) return st;
   SnReduce r;
   r.slab = g.slab;
-  const int spg = d->nseg / ngroups;
-  for (int gq = 0; gq < kMaxSeg; ++gq) r.dw[gq] = gq < ngroups ? dw[gq] : nullptr;
-  for (int gq = 0; gq <= kMaxSeg; ++gq) r.cb[gq] = gq <= ngroups ? p.cbase[gq * spg] : p.nch;
-  r.n_store = d->n_store;
+  const int spg = d.nseg / l.ngroups;
+  for (int gq = 0; gq < kMaxSeg; ++gq) r.dw[gq] = gq < l.ngroups ? dw[gq] : nullptr;
+  for (int gq = 0; gq <= kMaxSeg; ++gq) r.cb[gq] = gq <= l.ngroups ? l.cbase[gq * spg] : l.nsplit;
+  r.n_store = d.n_store;
   r.nw = g.nw;
-  r.per = (long)p.T * d->Cin * g.nw;
+  r.per = (long)g.T * d.Cin * g.nw;
   r.beta = beta;
-  hipLaunchKernelGGL(wgrad_sn_reduce_kernel, dim3((unsigned)((r.per + 255) / 256), ngroups), dim3(256), 0, s, r);
+  hipLaunchKernelGGL(wgrad_sn_reduce_kernel, dim3((unsigned)((r.per + 255) / 256), l.ngroups), dim3(256), 0, s, r);
   return cvl_launch_status();
 }

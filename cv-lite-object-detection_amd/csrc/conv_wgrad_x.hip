@@ -47,11 +47,10 @@ struct WxCfg {
   static constexpr int J = SR / (8 * RPI);  // DMA instructions per wave per operand and step
   static constexpr int KS = SR / BR;      // 32-deep MFMA sub-steps per step
 };
-constexpr int kMaxGroups = 2;
+constexpr int kMaxGroups = kWgXMaxGroups;
 #ifndef CVL_WGX_ABL
 #define CVL_WGX_ABL 0                     // measurement variants only (ablation bits, see issue())
 #endif
-constexpr unsigned kRecords = 0x7fffffffu;
 constexpr unsigned kOOB = 0x80000000u;
 
 struct WxArgs {
@@ -72,7 +71,7 @@ struct WxArgs {
 // tiles * nsplit) range holds it.  One launch per ResNet stage instead of one per conv: the per-launch
 // fixed cost (~7 us: prologue, epilogue, the grid's ramp) is paid once, and with the grid filled by
 // several problems each one needs fewer splits (fewer fp32 slab bytes to reduce).
-constexpr int kMaxProb = 16;
+constexpr int kMaxProb = kWgXMaxProb;
 struct WxProb {
   const cvl_bf16* x;
   const cvl_bf16* dy;
@@ -205,8 +204,8 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
   const int ry = tr_ - pad_t_, rx = ts_ - pad_l_;         // iy = oy * stride + ry
   const unsigned xcol = (unsigned)(ci * 2);
   const int rowb = ld_dy_ * 2, pixb = Cin_ * 2;
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)dyp, (short)0, (int)kRecords, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)src_, (short)0, (int)kRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)dyp, (short)0, (int)kConvBufRecords, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)src_, (short)0, (int)kConvBufRecords, 0x00020000);
 
   // ---- issue cursor ----------------------------------------------------------------------------
   // Per lane and DMA / load instruction j: the row's (local row, source iy, ix) and its two byte
@@ -543,12 +542,6 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
   }
 }
 
-struct WxPlan {
-  int T, SR, ngroups, spg, tiles, co_tiles, nsplit, chunk;
-  int g_m0[kMaxGroups], g_m1[kMaxGroups];
-  size_t slab;
-};
-
 #ifdef CVL_MEASURE
 // measurement builds: CVL_WGX_STAMPS=1 stamps every launch into this buffer (cvl_debug_wgx_stamps)
 constexpr int kStampWgs = 16384;
@@ -558,183 +551,92 @@ __device__ unsigned long long g_wgx_phase[kPhaseWgs * 8 * 8];
 int g_wgx_stamp_grid = 0;
 #endif
 
-// Modelled time of s splits at tile width T: rounds of 256 workgroups (one per CU; 512 for T = 128) x 32-row steps
-// per chunk (CVL_WGX_STEP, 0.01 us; ~0.8 us measured on the tower shape; CVL_WGX_STEP128 for the
-// 128-wide tile: also ~0.8 us measured -- two per CU, the step is bound by its DMA / barrier
-// overheads, not its MFMA work: the tower at 0.3 us picked 128 and took 323 us vs 232) + the fp32
-// slab round trip.  The 128-wide tile
-// serves the 1x1 / small-output launches (e.g. 1x1 256->1024 @ 32x32: 4 tiles of 256 -> 64 splits,
-// 64 MiB of slabs; 16 tiles of 128 -> 16 splits, 16 MiB).
-// K below one 256-deep tile (1x1 convs with Cin 128) leaves half of every 256 tile idle.
-inline bool wx_plan(const cvl_conv_desc* d, int ngroups, ConvArgs* a, WxPlan* p) {
-  if (cvl_dispatch_flag("wg_no_x")) return false;
-  if (cvl_conv_prepare(d, SEGM, a)) return false;
-  if (ngroups < 1 || ngroups > kMaxGroups || d->nseg % ngroups || d->relu_in || a->Npad % 64 || d->Cin % 8 ||
-      d->n_store % 4 || a->m_total < 1024)
+}  // namespace
+
+// What the X kernel can run: up to kMaxGroups groups, no ReLU on the source, 64-column output pieces,
+// 16-B dY / x pieces, at least 1024 rows, and every dY / source byte offset below the buffer-resource
+// bound (32-bit cursors).  a: the SEGM-padded layout of d.
+bool wg_x_fits(const cvl_conv_desc* d, int ngroups, const ConvArgs& a) {
+  if (ngroups < 1 || ngroups > kMaxGroups || d->nseg % ngroups || d->relu_in || a.Npad % 64 || d->Cin % 8 ||
+      d->n_store % 4 || a.m_total < 1024)
     return false;
-  // every dY / source byte offset must stay below the buffer-resource bound (32-bit cursors)
-  for (int i = 0; i < a->nseg; ++i) {
-    const ConvSeg& q = a->seg[i];
-    const long dy_end = (q.dst_base + (long)a->B * q.dst_img) * d->ld_dst * 2;
-    const long src_end = (q.src_base + (long)a->B * q.src_img) * a->Cin * 2;
-    if (dy_end >= (long)kRecords - 65536 || src_end >= (long)kRecords - 65536) return false;
+  for (int i = 0; i < a.nseg; ++i) {
+    const ConvSeg& q = a.seg[i];
+    const long dy_end = (q.dst_base + (long)a.B * q.dst_img) * d->ld_dst * 2;
+    const long src_end = (q.src_base + (long)a.B * q.src_img) * a.Cin * 2;
+    if (dy_end >= (long)kConvBufRecords - 65536 || src_end >= (long)kConvBufRecords - 65536) return false;
   }
-  p->ngroups = ngroups;
-  p->spg = d->nseg / ngroups;
-  int mg = 0;
-  for (int gq = 0; gq < ngroups; ++gq) {
-    p->g_m0[gq] = a->seg[gq * p->spg].m_start;
-    p->g_m1[gq] = (gq + 1) * p->spg < a->nseg ? a->seg[(gq + 1) * p->spg].m_start : a->m_total;
-    mg = p->g_m1[gq] - p->g_m0[gq] > mg ? p->g_m1[gq] - p->g_m0[gq] : mg;
-  }
-  for (int gq = ngroups; gq < kMaxGroups; ++gq) p->g_m0[gq] = p->g_m1[gq] = 0;
-  const int forced_t = cvl_tune_int("CVL_WGX_T", 0);
-  double best_t = 1e30;
-  int best_s = 0, best_T = 0;
-  int s256 = 0, tg256 = 0;
-  double t128 = 1e30;
-  int s128 = 0;
-  for (int T = 256; T >= 128; T /= 2) {
-    if (forced_t && forced_t != T) continue;
-    // T = 128 also takes 64-channel outputs (half of each tile idle: the stem's and the 1x1 ->64
-    // weight gradients, on the generic kernel at 149 / 44 / 37 us before)
-    if ((T == 256 && a->Npad % T) || a->K < cvl_tune_int(T == 256 ? "CVL_WGX_MIN_K" : "CVL_WGX_MIN_K128", T == 256 ? 256 : 64))
-      continue;
-    const int tg = ((a->Npad + T - 1) / T) * ((a->K + T - 1) / T) * ngroups;
-    const bool sr64 = T == 128 && cvl_tune_int("CVL_WGX_SR", 64) == 64;
-    const double step_us =
-        T == 256 ? cvl_tune_int("CVL_WGX_STEP", 80) / 100.0
-                 : (sr64 ? cvl_tune_int("CVL_WGX_STEP64", 120) / 200.0 : cvl_tune_int("CVL_WGX_STEP128", 80) / 100.0);
-    const double slab_us = (double)T * T * 4 * 2 / 5.0e6 * cvl_tune_int("CVL_WGX_SLAB_PCT", 100) / 100.0;
-    int max_s = mg / 512;
-    if (max_s < 1) max_s = 1;
-    if (max_s > 2048 / tg) max_s = 2048 / tg > 1 ? 2048 / tg : 1;
-    const int per_round = T == 256 || sr64 ? 256 : 512;   // the 32-row 128-wide tile (80 KiB of LDS): 2 per CU
-    for (int s = 1; s <= max_s; ++s) {
-      const int rounds = (tg * s + per_round - 1) / per_round;
-      const int chunk = ((mg + s - 1) / s + SEGM - 1) / SEGM * SEGM;
-      const double t = rounds * (chunk / BR) * step_us + (s > 1 ? tg * s * slab_us : 0.0);
-      if (t < best_t) { best_t = t; best_s = s; best_T = T; }
-      if (T == 256 && best_T == 256) { s256 = best_s; tg256 = tg; }
-      if (T == 128 && t < t128) { t128 = t; s128 = s; }
-    }
-  }
-  // a 256-wide plan that cannot occupy every CU (tiles x splits < 256: the 1x1 / small-output
-  // launches, capped by the 512-row minimum chunk) loses to the 128-wide one in the per-shape
-  // sweep (1x1 256->1024 @ 32x32: 38 -> 31 us; 3x3 s2 2048->256 @ 8x8: 45 -> 34 us); the tower
-  // (18 tiles x 14 splits) keeps 256 (230 vs 322 us)
-  if (best_T == 256 && s128 && tg256 * s256 < 240 && !cvl_tune_flag("CVL_WGX_KEEP256")) {
-    best_T = 128;
-    best_s = s128;
-  }
-  if (!best_T) return false;
-  p->T = best_T;
-  // 64-row steps on the 128-wide tile (CVL_WGX_SR=32 reverts): one workgroup per CU, half the
-  // splits of the 32-row form at the same workgroup count per CU-round -- half the slab bytes (in-step
-  // trace: the reductions 90 -> 63 / 133 -> 100 us per batch, the kernels +1-3 us; FCOS +0.6 %)
-  p->SR = best_T == 128 && cvl_tune_int("CVL_WGX_SR", 64) == 64 ? 64 : 32;
-  p->co_tiles = (a->Npad + best_T - 1) / best_T;
-  p->tiles = p->co_tiles * ((a->K + best_T - 1) / best_T);
-  const int forced = cvl_tune_int("CVL_WGX_SPLITS", 0);
-  if (forced > 0) best_s = forced;
-  p->chunk = ((mg + best_s - 1) / best_s + SEGM - 1) / SEGM * SEGM;
-  p->nsplit = (mg + p->chunk - 1) / p->chunk;
-  p->slab = p->nsplit > 1 ? (size_t)ngroups * p->nsplit * a->K * d->n_store * sizeof(float) : 0;
   return true;
 }
 
-}  // namespace
-
-// Workspace the X path needs (>= 16), or -1 when the launch does not qualify.
-long cvl_conv_wgrad_x_workspace(const cvl_conv_desc* d, int ngroups) {
-  ConvArgs a;
-  WxPlan p;
-  if (!wx_plan(d, ngroups, &a, &p)) return -1;
-  return (long)(p.slab > 16 ? p.slab : 16);
-}
-
-// Returns -1 when the launch does not qualify (the caller takes another kernel), else a status.
-int cvl_conv_wgrad_x(const cvl_conv_desc* d, int ngroups, const void* x, const void* dy, float* const* dw,
-                     float beta, void* workspace, size_t workspace_bytes, hipStream_t s) {
+int launch_wg_x(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const void* dy, float* const* dw, float beta,
+                void* ws, hipStream_t s) {
   WxArgs g;
-  WxPlan p;
-  if (!wx_plan(d, ngroups, &g.a, &p)) return -1;
-  if (!workspace || workspace_bytes < (p.slab > 16 ? p.slab : 16)) return CVL_EINVAL;
+  int st = cvl_conv_prepare(&d, SEGM, &g.a);
+  if (st) return st;
+  const int ngroups = l.ngroups;
   g.stamps = nullptr;
   g.phase = nullptr;
   g.ablate = 0;
 #ifdef CVL_MEASURE
   static const bool stamps = cvl_tune_flag("CVL_WGX_STAMPS");
-  if (stamps && p.tiles * p.nsplit * ngroups <= kStampWgs) {
+  if (stamps && l.tiles * l.nsplit * ngroups <= kStampWgs) {
     void* sym = nullptr;
     if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_wgx_stamps)) == hipSuccess) g.stamps = (unsigned long long*)sym;
-    if (p.tiles * p.nsplit * ngroups <= kPhaseWgs && hipGetSymbolAddress(&sym, HIP_SYMBOL(g_wgx_phase)) == hipSuccess)
+    if (l.tiles * l.nsplit * ngroups <= kPhaseWgs && hipGetSymbolAddress(&sym, HIP_SYMBOL(g_wgx_phase)) == hipSuccess)
       g.phase = (unsigned long long*)sym;
     g.ablate = cvl_tune_int("CVL_WGX_ABLATE", 0);
-    g_wgx_stamp_grid = p.tiles * p.nsplit * ngroups;
+    g_wgx_stamp_grid = l.tiles * l.nsplit * ngroups;
   }
 #endif
   g.a.src = reinterpret_cast<const cvl_bf16*>(x);
   g.dy = reinterpret_cast<const cvl_bf16*>(dy);
-  g.ld_dy = d->ld_dst;
-  g.dy_coff = d->dst_coff;
-  g.Cout = d->n_store;
+  g.ld_dy = d.ld_dst;
+  g.dy_coff = d.dst_coff;
+  g.Cout = d.n_store;
   g.beta = beta;
-  g.co_tiles = p.co_tiles;
-  g.tiles = p.tiles;
-  g.nsplit = p.nsplit;
-  g.chunk = p.chunk;
-  g.direct = p.nsplit == 1;
-  const size_t per_group = (size_t)p.nsplit * g.a.K * g.Cout;
+  g.co_tiles = l.co_tiles;
+  g.tiles = l.tiles;
+  g.nsplit = l.nsplit;
+  g.chunk = l.chunk;
+  g.direct = l.nsplit == 1;
+  const size_t per_group = (size_t)l.nsplit * g.a.K * g.Cout;
   for (int gq = 0; gq < kMaxGroups; ++gq) {
-    g.g_m0[gq] = p.g_m0[gq];
-    g.g_m1[gq] = p.g_m1[gq];
+    g.g_m0[gq] = l.g_m0[gq];
+    g.g_m1[gq] = l.g_m1[gq];
     const int gs = gq < ngroups ? gq : 0;
-    g.out[gq] = g.direct ? dw[gs] : reinterpret_cast<float*>(workspace) + gs * per_group;
+    g.out[gq] = g.direct ? dw[gs] : reinterpret_cast<float*>(ws) + gs * per_group;
   }
-  g_cvl_conv_last_kernel = CVL_CK_WG_X;
-  if (g.direct) {                               // writes dW now: a queued reduction into it first
-    int gs = cvl_wgrad_defer_guard(dw[0], s);
-    if (!gs && ngroups > 1) gs = cvl_wgrad_defer_guard(dw[1], s);
-    if (gs) return gs;
-  }
-  const dim3 grid(p.tiles * p.nsplit * ngroups);
+  const dim3 grid(l.tiles * l.nsplit * ngroups);
 #ifdef CVL_MEASURE
   if (g.stamps) {
-    if (p.T == 256) hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, true>), grid, dim3(NT), 0, s, g);
-    else if (p.SR == 64) hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, true>), grid, dim3(NT), 0, s, g);
+    if (l.tile == 256) hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, true>), grid, dim3(NT), 0, s, g);
+    else if (l.rows == 64) hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, true>), grid, dim3(NT), 0, s, g);
     else hipLaunchKernelGGL((conv_wgrad_x_kernel<128, BR, true>), grid, dim3(NT), 0, s, g);
   } else
 #endif
-  if (p.T == 256) {
-    if (!cvl_dispatch_flag("wg_no_pf")) hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, true>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR>), grid, dim3(NT), 0, s, g);
-  } else if (p.SR == 64) {
-    if (!cvl_dispatch_flag("wg_no_pf")) hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, true>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64>), grid, dim3(NT), 0, s, g);
+  if (l.tile == 256) {
+    with_bool(l.pf, [&](auto PF) {
+      hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, decltype(PF)::value>), grid, dim3(NT), 0, s, g);
+    });
+  } else if (l.rows == 64) {
+    with_bool(l.pf, [&](auto PF) {
+      hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, decltype(PF)::value>), grid, dim3(NT), 0, s, g);
+    });
   } else {
     hipLaunchKernelGGL((conv_wgrad_x_kernel<128, BR>), grid, dim3(NT), 0, s, g);
   }
-  int st = cvl_launch_status();
+  st = cvl_launch_status();
   if (st || g.direct) return st;
-  return cvl_wgrad_reduce((const float*)workspace, dw[0], ngroups > 1 ? dw[1] : dw[0], (long)g.a.K * g.Cout / 4,
-                          p.nsplit, ngroups, beta, s);
+  return cvl_wgrad_reduce((const float*)ws, dw[0], ngroups > 1 ? dw[1] : dw[0], (long)g.a.K * g.Cout / 4, l.nsplit,
+                          ngroups, beta, s);
 }
 
 // ---- batched 1x1 weight gradients (cvl_conv_wgrad_batch) -------------------------------------------
-namespace {
-
-// tile width of a batched problem: 256 (the tower kernel's tile, ~2x its MFMA rate per CU) when
-// both GEMM sides fill it (Npad % 256 == 0, Cin >= 256: the conv4_x / conv5_x 1x1 convs and the
-// 256 -> 512 projections), else 128; one launch per tile width
-inline int wx_batch_t(const cvl_conv_desc* d, const ConvArgs& a) {
-  return (a.Npad % 256 == 0 && d->Cin >= 256 && !cvl_dispatch_flag("wgb_no_256")) ? 256 : 128;
-}
-
 // a problem the batched kernel takes: bf16, one dense segment (bases 0, rows = images x map), 1x1,
 // pad 0, stride 1 or 2, the wgrad_x operand constraints (16-B dY / x pieces, 32-bit offsets)
-bool wx_batch_ok(const cvl_conv_desc* d, ConvArgs* a) {
-  if (!d || d->prec != CVL_PREC_BF16 || d->mode != CVL_CONV_FWD || d->nseg != 1 || d->KH != 1 || d->KW != 1 ||
+bool wg_x_batch_fits(const cvl_conv_desc* d, ConvArgs* a) {
+  if (d->prec != CVL_PREC_BF16 || d->mode != CVL_CONV_FWD || d->nseg != 1 || d->KH != 1 || d->KW != 1 ||
       d->pad_t || d->pad_l || (d->stride != 1 && d->stride != 2) || d->relu_in)
     return false;
   if (cvl_conv_prepare(d, SEGM, a)) return false;
@@ -744,218 +646,49 @@ bool wx_batch_ok(const cvl_conv_desc* d, ConvArgs* a) {
   if (q.src_base || q.dst_base || q.src_img != (int64_t)q.Hs * q.Ws || q.dst_img != (int64_t)q.Hr * q.Wr) return false;
   if (q.Hr != (q.Hs + d->stride - 1) / d->stride || q.Wr != (q.Ws + d->stride - 1) / d->stride) return false;
   const long dy_end = (long)d->B * q.dst_img * d->ld_dst * 2, src_end = (long)d->B * q.src_img * d->Cin * 2;
-  return dy_end < (long)kRecords - 65536 && src_end < (long)kRecords - 65536;
+  return dy_end < (long)kConvBufRecords - 65536 && src_end < (long)kConvBufRecords - 65536;
 }
 
-// Plan of one launch over problems idx[0..n): a common chunk length (rows per workgroup) for all of
-// them, chosen by the same cost model as wx_plan -- rounds of one workgroup per CU x (fixed cost +
-// 64-row steps) + the fp32 slab round trip of split problems.  Measured (round 6, 1x1 1024->256 @
-// 32x32 at 16 / 8 / 4 / 2 / 1 splits: 20.6 / 29.5 / 48.2 / 89.1 / 171 us): ~7.2 us per workgroup
-// round + ~0.64 us per step.
-struct WxBatchPlan {
+int launch_wg_x_batch(const WgBatchLaunch& b, const cvl_conv_desc* const* d, const void* const* x, const void* const* dy,
+                      float* const* dw, float beta, char* ws, hipStream_t s) {
   WxBatchArgs g;
-  size_t slab_off[kMaxProb];               // byte offset of problem i's slab in the workspace
-  size_t bytes;                            // workspace bytes of the slabs
-  int wgs;
-};
-
-void wx_batch_plan(const cvl_conv_desc* const* d, const int* idx, int n, int T, WxBatchPlan* pl) {
-  ConvArgs a[kMaxProb];
-  int tiles[kMaxProb], mt[kMaxProb], maxm = 0;
-  for (int i = 0; i < n; ++i) {
-    wx_batch_ok(d[idx[i]], &a[i]);
-    tiles[i] = ((a[i].Npad + T - 1) / T) * ((a[i].K + T - 1) / T);
-    mt[i] = a[i].m_total;
-    maxm = mt[i] > maxm ? mt[i] : maxm;
-  }
-  static const int ncu = cvl_device_cus();
-  // per-row costs: 128-wide tile ~0.64 us per 64-row step; 256-wide ~0.54 us per 32-row step (the
-  // tower's weight gradient: 390 steps in ~210 us)
-  const double fix = cvl_tune_int("CVL_WGB_FIX", 720) / 100.0;
-  const double step = T == 256 ? cvl_tune_int("CVL_WGB_STEP256", 54) / 100.0 : cvl_tune_int("CVL_WGB_STEP", 64) / 100.0;
-  const int srows = T == 256 ? BR : 64;
-  const double slab_us = (double)T * T * 4 * 2 / 5.0e6;
-  int best_c = maxm;
-  double best_t = 1e30;
-  for (int c = SEGM; ; c *= 2) {
-    const int cc = c < maxm ? c : maxm;
-    long w = 0, sl = 0;
-    for (int i = 0; i < n; ++i) {
-      const int sp = (mt[i] + cc - 1) / cc;
-      w += (long)tiles[i] * sp;
-      if (sp > 1) sl += (long)tiles[i] * sp;
-    }
-    const double t = (double)((w + ncu - 1) / ncu) * (fix + (cc / srows) * step) + sl * slab_us;
-    if (t < best_t) {
-      best_t = t;
-      best_c = cc;
-    }
-    if (cc >= maxm) break;
-  }
-  const int forced = cvl_tune_int("CVL_WGB_CHUNK", 0);   // measurement: rows per workgroup
-  if (forced > 0) best_c = (forced + SEGM - 1) / SEGM * SEGM;
-  pl->g.n = n;
-  pl->g.stamps = nullptr;
-  pl->g.phase = nullptr;
-  pl->g.ablate = 0;
-  size_t off = 0;
+  g.n = b.n;
+  g.stamps = nullptr;
+  g.phase = nullptr;
+  g.ablate = 0;
+  const int T = b.tile;
   int wg = 0;
-  for (int i = 0; i < n; ++i) {
-    const cvl_conv_desc* q = d[idx[i]];
-    WxProb& P = pl->g.p[i];
+  for (int i = 0; i < b.n; ++i) {
+    const int pi = b.idx[i];
+    const cvl_conv_desc* q = d[pi];
+    WxProb& P = g.p[i];
     P.Hr = q->seg[0].Hr; P.Wr = q->seg[0].Wr; P.Hs = q->seg[0].Hs; P.Ws = q->seg[0].Ws;
     P.B = q->B; P.Cin = q->Cin; P.stride = q->stride;
     P.Cout = q->n_store; P.ld_dy = q->ld_dst; P.dy_coff = q->dst_coff;
-    P.co_tiles = (a[i].Npad + T - 1) / T;
-    P.tiles = tiles[i];
-    P.chunk = best_c;
-    P.nsplit = (mt[i] + best_c - 1) / best_c;
+    P.co_tiles = (q->Npad + T - 1) / T;
+    P.tiles = P.co_tiles * ((q->Cin + T - 1) / T);
+    P.chunk = b.chunk;
+    P.nsplit = b.nsplit[i];
     P.direct = P.nsplit == 1;
-    P.m_total = mt[i];
+    P.m_total = (P.B * P.Hr * P.Wr + SEGM - 1) / SEGM * SEGM;
     P.wg0 = wg;
     wg += P.tiles * P.nsplit;
-    pl->slab_off[i] = off;
-    if (!P.direct) off += ((size_t)P.nsplit * a[i].K * P.Cout * sizeof(float) + 255) & ~(size_t)255;
+    P.x = reinterpret_cast<const cvl_bf16*>(x[pi]);
+    P.dy = reinterpret_cast<const cvl_bf16*>(dy[pi]);
+    P.out = P.direct ? dw[pi] : reinterpret_cast<float*>(ws + b.slab_off[i]);
+    P.beta = beta;
   }
-  for (int i = n; i < kMaxProb; ++i) pl->g.p[i].wg0 = 0x7fffffff;
-  pl->bytes = off;
-  pl->wgs = wg;
-}
-
-}  // namespace
-
-bool cvl_wgrad_h_batch_ok(const cvl_conv_desc* d);            // conv_wgrad_h.hip
-int cvl_wgrad_h_batch_max();
-size_t cvl_wgrad_h_batch_workspace(const cvl_conv_desc* const* d, const int* idx, int n);
-int cvl_wgrad_h_batch(const cvl_conv_desc* const* d, const int* idx, int n, const void* const* x, const void* const* dy,
-                      float* const* dw, float beta, void* workspace, hipStream_t s);
-
-namespace {
-
-// problems of the batch in launch groups: <= kMaxProb 1x1 problems of one tile width (256-wide
-// groups first; f(d, idx, k, T)), then the 3x3 problems the halo weight-gradient kernel takes
-// (f(d, idx, k, 3)), the rest individually (f(nullptr, {i}, 1, 0)); the workspace holds each launch
-// group's slabs, then each individual problem's own workspace, in this order
-bool wx_batch_wh(const cvl_conv_desc* d) {
-  return !cvl_dispatch_flag("wgb_no_h") && d->prec == CVL_PREC_BF16 && cvl_wgrad_h_batch_ok(d);
-}
-
-template <typename F>
-int wx_batch_walk(const cvl_conv_desc* const* d, int n, F&& f) {
-  ConvArgs a;
-  {
-    const int mh = cvl_wgrad_h_batch_max();
-    int idx[kMaxProb], k = 0;
-    for (int i = 0; i < n; ++i) {
-      if (wx_batch_ok(d[i], &a) || !wx_batch_wh(d[i])) continue;
-      idx[k++] = i;
-      if (k == mh) {
-        const int st = f(d, idx, k, 3);
-        if (st) return st;
-        k = 0;
-      }
-    }
-    if (k) {
-      const int st = f(d, idx, k, 3);
-      if (st) return st;
-    }
+  for (int i = b.n; i < kMaxProb; ++i) g.p[i].wg0 = 0x7fffffff;
+  if (T == 256)
+    hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, true, WxBatchArgs>), dim3(wg), dim3(NT), 0, s, g);
+  else
+    hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, true, WxBatchArgs>), dim3(wg), dim3(NT), 0, s, g);
+  int st = cvl_launch_status();
+  for (int i = 0; !st && i < b.n; ++i) {
+    const WxProb& P = g.p[i];
+    if (!P.direct) st = cvl_wgrad_reduce(P.out, dw[b.idx[i]], dw[b.idx[i]], (long)P.Cin * P.Cout / 4, P.nsplit, 1, beta, s);
   }
-  for (int T = 256; T >= 128; T /= 2) {
-    int idx[kMaxProb], k = 0;
-    for (int i = 0; i < n; ++i) {
-      if (!wx_batch_ok(d[i], &a) || wx_batch_t(d[i], a) != T) continue;
-      idx[k++] = i;
-      if (k == kMaxProb) {
-        const int st = f(d, idx, k, T);
-        if (st) return st;
-        k = 0;
-      }
-    }
-    if (k) {
-      const int st = f(d, idx, k, T);
-      if (st) return st;
-    }
-  }
-  for (int i = 0; i < n; ++i) {
-    if (wx_batch_ok(d[i], &a) || wx_batch_wh(d[i])) continue;
-    const int st = f(nullptr, &i, 1, 0);           // individual
-    if (st) return st;
-  }
-  return CVL_OK;
-}
-
-}  // namespace
-
-extern "C" size_t cvl_conv_wgrad_batch_workspace_size(const cvl_conv_desc* const* d, int n) {
-  if (!d || n < 1) return 16;
-  size_t total = 0;
-  wx_batch_walk(d, n, [&](const cvl_conv_desc* const* dd, const int* idx, int k, int T) {
-    if (!dd) {
-      total += (cvl_conv_wgrad_workspace_size(d[idx[0]]) + 255) & ~(size_t)255;
-    } else if (T == 3) {
-      total += cvl_wgrad_h_batch_workspace(dd, idx, k);
-    } else {
-      WxBatchPlan pl;
-      wx_batch_plan(dd, idx, k, T, &pl);
-      total += pl.bytes;
-    }
-    return CVL_OK;
-  });
-  return total > 16 ? total : 16;
-}
-
-extern "C" int cvl_conv_wgrad_batch(const cvl_conv_desc* const* d, int n, const void* const* x, const void* const* dy,
-                                    float* const* dw, float beta, void* workspace, size_t workspace_bytes,
-                                    cvl_stream_t stream) {
-  CVL_CHECK_ARG(d && x && dy && dw && n >= 1);
-  for (int i = 0; i < n; ++i) {
-    CVL_CHECK_ARG(d[i] && x[i] && dy[i] && dw[i]);
-    for (int j = 0; j < i; ++j) CVL_CHECK_ARG(dw[j] != dw[i]);
-  }
-  CVL_CHECK_ARG(workspace && workspace_bytes >= cvl_conv_wgrad_batch_workspace_size(d, n));
-  hipStream_t s = (hipStream_t)stream;
-  for (int i = 0; i < n; ++i) {                   // a pending reduction into one of these dW lands first
-    const int gs = cvl_wgrad_defer_guard(dw[i], s);
-    if (gs) return gs;
-  }
-  char* ws = reinterpret_cast<char*>(workspace);
-  size_t used = 0;
-  return wx_batch_walk(d, n, [&](const cvl_conv_desc* const* dd, const int* idx, int k, int T) {
-    const int i0 = idx[0];
-    if (!dd) {                                    // a problem the batched kernel does not take
-      const size_t w = cvl_conv_wgrad_workspace_size(d[i0]);
-      const int st = cvl_conv_wgrad(d[i0], x[i0], dy[i0], dw[i0], beta, ws + used, w, stream);
-      used += (w + 255) & ~(size_t)255;
-      return st;
-    }
-    if (T == 3) {                                 // 3x3 problems on the halo weight-gradient kernel
-      const int st = cvl_wgrad_h_batch(dd, idx, k, x, dy, dw, beta, ws + used, s);
-      used += cvl_wgrad_h_batch_workspace(dd, idx, k);
-      return st;
-    }
-    WxBatchPlan pl;
-    wx_batch_plan(dd, idx, k, T, &pl);
-    for (int i = 0; i < k; ++i) {
-      WxProb& P = pl.g.p[i];
-      P.x = reinterpret_cast<const cvl_bf16*>(x[idx[i]]);
-      P.dy = reinterpret_cast<const cvl_bf16*>(dy[idx[i]]);
-      P.out = P.direct ? dw[idx[i]] : reinterpret_cast<float*>(ws + used + pl.slab_off[i]);
-      P.beta = beta;
-    }
-    g_cvl_conv_last_kernel = CVL_CK_WG_X;
-    if (T == 256)
-      hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, true, WxBatchArgs>), dim3(pl.wgs), dim3(NT), 0, s, pl.g);
-    else
-      hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, true, WxBatchArgs>), dim3(pl.wgs), dim3(NT), 0, s, pl.g);
-    int st = cvl_launch_status();
-    for (int i = 0; !st && i < k; ++i) {
-      const WxProb& P = pl.g.p[i];
-      if (P.direct) continue;
-      st = cvl_wgrad_reduce(P.out, dw[idx[i]], dw[idx[i]], (long)P.Cin * P.Cout / 4, P.nsplit, 1, beta, s);
-    }
-    used += pl.bytes;
-    return st;
-  });
+  return st;
 }
 
 #ifdef CVL_MEASURE

@@ -82,6 +82,8 @@ SIGNATURES = {
     "cvl_conv_wgrad_grouped": (c_int, [P, c_int, P, P, P, c_float, P, c_size_t, P]),
     "cvl_conv_wgrad_batch_workspace_size": (c_size_t, [P, c_int]),
     "cvl_conv_wgrad_batch": (c_int, [P, c_int, P, P, P, c_float, P, c_size_t, P]),
+    "cvl_conv_wgrad_plan": (c_int, [P, c_int, P, P, P, P]),
+    "cvl_conv_wgrad_batch_plan": (c_int, [P, c_int, P, P, P]),
     "cvl_pack_conv_weights": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P]),
     "cvl_pack_conv_weights_multi": (c_int, [P, P, c_int, P]),
     "cvl_im2col": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -225,7 +227,7 @@ _lib = None
 NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_plan_bnsum", "cvl_conv_igemm_plan_grid",
          "cvl_conv_igemm_dgrad_bnsum_res_bits", "cvl_bn_finalize_apply_bits", "cvl_bn_finalize_apply_bnres_bits",
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
-         "cvl_bn_backward_sc_bits"}
+         "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan"}
 
 
 def load():

@@ -265,6 +265,18 @@ size_t cvl_conv_wgrad_batch_workspace_size(const cvl_conv_desc* const* d, int n)
 int cvl_conv_wgrad_batch(const cvl_conv_desc* const* d, int n, const void* const* x, const void* const* dy,
                          float* const* dw, float beta, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
 
+/* Test and profiling hooks: what cvl_conv_wgrad_grouped(d, ngroups, ...) would launch, as
+ * cvl_conv_igemm_plan for the other half.  Host only: no device memory, no launch.  *kernel (a
+ * CVL_CK_WG_* code), *tile (its co tile width) and *nsplit describe the call's LAST launch -- what
+ * cvl_conv_igemm_last_kernel() shows after it -- and *workspace is the call's workspace size.  A
+ * descriptor the call rejects gets the same status; prec == CVL_PREC_F32 reports CVL_CK_NONE. */
+int cvl_conv_wgrad_plan(const cvl_conv_desc* d, int ngroups, int32_t* kernel, int32_t* tile, int32_t* nsplit,
+                        size_t* workspace);
+/* ... and of cvl_conv_wgrad_batch(d, n, ...), per problem (arrays of n): its kernel, the index of
+ * the launch group that runs it (in launch order) and its split count. */
+int cvl_conv_wgrad_batch_plan(const cvl_conv_desc* const* d, int n, int32_t* kernel_of, int32_t* launch_of,
+                              int32_t* nsplit_of);
+
 /* fp32 HWIO [KH][KW][Cin][Cout] master weights -> bf16 forward pack [Npad][KH*KW*Cin_k]
  * (zero rows >= Cout and channels >= Cin) and/or dgrad pack [Cin_pad][KH*KW*Cout_pad]. */
 int cvl_pack_conv_weights(const float* w_hwio, int KH, int KW, int Cin, int Cout, int Cin_k, int Npad,
