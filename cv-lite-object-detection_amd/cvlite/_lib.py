@@ -151,6 +151,16 @@ SIGNATURES = {
     "cvl_depthwise_wgrad_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cvl_depthwise_wgrad": (c_int, [P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, P, c_size_t, P]),
+    "cvl_gconv3x3_packed_bytes": (c_size_t, [c_int]),
+    "cvl_gconv3x3_pack": (c_int, [P, c_int, c_int, P, P, P]),
+    "cvl_gconv3x3_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "cvl_gconv3x3_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "cvl_gconv3x3_wgrad_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cvl_gconv3x3_wgrad": (c_int, [P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P,
+                                   c_size_t, P]),
+    "cvl_bn_data_stats_workspace_size": (c_size_t, [c_int]),
+    "cvl_bn_data_stats": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, c_size_t, P]),
+    "cvl_bn_data_apply": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "cvl_reshape_concat": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
     "cvl_reshape_concat_backward": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
     "cvl_bias_scalar_fold_periodic": (c_int, [P, P, P, c_int, c_int, c_int, P]),

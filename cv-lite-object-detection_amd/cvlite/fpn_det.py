@@ -20,6 +20,7 @@ from .layers import BF16, Conv, ParamStore, act_dtype, wgrad_batch
 from .layers import conv_wgrad as wgrad_collect
 from .mobilenet_v2 import MobileNetV2
 from .resnet import ResNet50
+from .resnext import ResNeXt
 from . import _lib
 
 FPN_C = 256
@@ -70,7 +71,10 @@ class FPNDetector(object):
         self.cls_tower = [Conv(st, "cls_layer_%d" % (i + 1), 3, FPN_C, FPN_C, bias=False) for i in range(4)]
         self.reg_tower = [Conv(st, "reg_layer_%d" % (i + 1), 3, FPN_C, FPN_C, bias=False) for i in range(4)]
         kind = getattr(self, "backbone_model", "resnet50")
-        self.backbone = MobileNetV2(st) if kind == "mobilenetv2" else ResNet50(st, kind)
+        if kind.startswith("resnext"):
+            self.backbone = ResNeXt(st, kind)
+        else:
+            self.backbone = MobileNetV2(st) if kind == "mobilenetv2" else ResNet50(st, kind)
         t3, t4, t5 = self.backbone.tap_channels
         self.c3_1x1 = Conv(st, "c3_1x1", 1, t3, FPN_C)
         self.c4_1x1 = Conv(st, "c4_1x1", 1, t4, FPN_C)
@@ -112,6 +116,8 @@ class FPNDetector(object):
                     entries += c.pack_entries()
             self._pack_plan = nn.PackPlan(entries, self.device)
         self._pack_plan.run()
+        if isinstance(self.backbone, ResNeXt):          # the grouped 3x3 kernels' slab images
+            self.backbone.pack_grouped()
 
     # ---- geometry ---------------------------------------------------------------------------------
     @staticmethod
@@ -235,6 +241,8 @@ class FPNDetector(object):
                             self.c6_3x3, self.c7_3x3]))]
         if isinstance(bb, MobileNetV2):
             return g + [("backbone", bb.param_names())]
+        if isinstance(bb, ResNeXt):
+            return g + bb.grad_groups()
         for si in (3, 2, 1):
             g.append(("conv%d" % (si + 2), units([u for b in bb.stages[si] for u in b.units()])))
         stem = [bb.stem.conv.wname, bb.stem.conv.bname, bb.stem.bn.gname, bb.stem.bn.bname]

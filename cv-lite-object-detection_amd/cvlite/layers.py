@@ -380,10 +380,10 @@ class ConvBN(object):
     """conv -> BN (-> + residual) (-> ReLU): the Keras ResNet50 unit."""
 
     def __init__(self, store, name, k, cin, cout, stride=1, pad="same", dgrad=True, cin_k=None,
-                 bn_name=None):
+                 bn_name=None, bias=True, eps=1.001e-5, momentum=0.99):
         self.conv = Conv(store, name + "_conv" if bn_name is None else name, k, cin, cout, stride, pad,
-                         bias=True, dgrad=dgrad, cin_k=cin_k)
-        self.bn = BatchNorm(store, (name + "_bn") if bn_name is None else bn_name, cout)
+                         bias=bias, dgrad=dgrad, cin_k=cin_k)
+        self.bn = BatchNorm(store, (name + "_bn") if bn_name is None else bn_name, cout, eps=eps, momentum=momentum)
 
     def forward(self, x, B, H, W, relu=True, residual=None, train=True, arena=None, defer=False,
                 residual_bn=None):

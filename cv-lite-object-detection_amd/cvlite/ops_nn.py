@@ -455,6 +455,63 @@ def depthwise_wgrad(x, dy, dw, k, stride, pad_t, pad_l, beta=0.0):
               int(pad_t), int(pad_l), Ho, Wo, ptr(ws), ws.numel(), stream())
 
 
+# ---- grouped 3x3 conv (include/cvlite.h "Grouped 3x3 convolution"; the ResNeXt bottleneck) --------
+def gconv3x3_packed(C, device):
+    """An empty bf16 slab image of a grouped kernel with C channels (cvl_gconv3x3_packed_bytes)."""
+    n = int(_lib.load().cvl_gconv3x3_packed_bytes(int(C)))
+    if n == 0:
+        raise _lib.CvlError("grouped 3x3 conv: C = %d is not a multiple of 32" % C)
+    return torch.empty(n // 2, dtype=BF16, device=device)
+
+
+def gconv3x3_pack(w, w_fwd=None, w_dgrad=None):
+    """fp32 master w [3,3,Cg,C] -> the bf16 forward and / or data-gradient images."""
+    Cg, C = int(w.shape[2]), int(w.shape[3])
+    _lib.call("cvl_gconv3x3_pack", ptr(w), C, Cg, ptr(w_fwd), ptr(w_dgrad), stream())
+
+
+def gconv3x3_fwd(x, w_fwd, y, Cg, stride, stats=None):
+    """x [B,H,W,C] bf16 -> y [B,Ho,Wo,C] bf16 (pad 1, Ho = (H - 1) // stride + 1); stats: BN accumulators."""
+    B, H, W, C = x.shape
+    Ho, Wo = y.shape[1], y.shape[2]
+    _lib.call("cvl_gconv3x3_fwd", ptr(x), ptr(w_fwd), ptr(y), acc_ptr(stats), B, H, W, C, int(Cg), int(stride), Ho, Wo,
+              stream())
+
+
+def gconv3x3_dgrad(dy, w_dgrad, dx, Cg, stride, beta=0.0):
+    B, H, W, C = dx.shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    _lib.call("cvl_gconv3x3_dgrad", ptr(dy), ptr(w_dgrad), ptr(dx), B, H, W, C, int(Cg), int(stride), Ho, Wo,
+              float(beta), stream())
+
+
+def gconv3x3_wgrad(x, dy, dw, stride, beta=0.0):
+    """dw [3,3,Cg,C] fp32 = beta*dw + the weight gradient (deterministic)."""
+    B, H, W, C = x.shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    Cg = int(dw.shape[2])
+    n = int(_lib.load().cvl_gconv3x3_wgrad_workspace_size(B, H, W, C, Cg, int(stride)))
+    ws = torch.empty(max(n, 16), dtype=torch.uint8, device=x.device)
+    _lib.call("cvl_gconv3x3_wgrad", ptr(x), ptr(dy), ptr(dw), float(beta), B, H, W, C, Cg, int(stride), Ho, Wo,
+              ptr(ws), ws.numel(), stream())
+
+
+def bn_data_stats(img, mean_rstd, run_mean, run_var, eps, momentum):
+    """Per-image (mean, rstd) [B,3,2] of the fp32 image [B,H,W,3] + the moving-average update."""
+    B, H, W, C = img.shape
+    assert C == 3 and img.dtype == torch.float32 and img.is_contiguous()
+    n = int(_lib.load().cvl_bn_data_stats_workspace_size(B))
+    ws = torch.empty(n, dtype=torch.uint8, device=img.device)
+    _lib.call("cvl_bn_data_stats", ptr(img), B, H, W, float(eps), float(momentum), ptr(mean_rstd), ptr(run_mean),
+              ptr(run_var), ptr(ws), n, stream())
+
+
+def bn_data_apply(img, mean_rstd, beta, out):
+    B, H, W, C = img.shape
+    assert C == 3 and img.dtype == torch.float32 and img.is_contiguous() and out.is_contiguous()
+    _lib.call("cvl_bn_data_apply", ptr(img), ptr(mean_rstd), ptr(beta), ptr(out), B, H, W, stream())
+
+
 def conv_igemm_dgrad_bnsum(desc, src, dst, z, mean_rstd, gamma, beta, sums, act_hi=float("inf"), zero=True):
     """DGRAD conv whose epilogue also forms the next BN's backward first pass into `sums`
     (bn_acc [B][C][2][S], zeroed here first unless zero=False: the caller's buffer is already zero).

@@ -23,14 +23,11 @@ from .layers import Conv
 class RetinaNetNet(FPNDetector):
     @staticmethod
     def backbone_kind(name):
-        """RetinaNet/retinanet_module.py:30-71: ResNet50 / 101 / 152, ResNeXt50 / 101 (third-party
-        classification_models, not built), every other name MobileNetV2."""
+        """RetinaNet/retinanet_module.py:30-71: ResNet50 / 101 / 152, ResNeXt50 / 101 (the third-party
+        classification_models graphs, restated in resnext.py), every other name MobileNetV2."""
         n = name.lower()
-        if n in ("resnet50", "resnet101", "resnet152"):
+        if n in ("resnet50", "resnet101", "resnet152", "resnext50", "resnext101"):
             return n
-        if n in ("resnext50", "resnext101"):
-            raise NotImplementedError("the ResNeXt backbones come from the third-party classification_models "
-                                      "package; cvlite builds the ResNet and MobileNetV2 branches")
         return "mobilenetv2"
 
     A = 9

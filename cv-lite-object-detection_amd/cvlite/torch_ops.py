@@ -8,6 +8,9 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           explicit pad), NHWC bf16, HWIO fp32
                                                           master weights; autograd = the dgrad /
                                                           wgrad / bias-grad kernels
+  torch.ops.cvlite.group_conv3x3_nhwc(x, w, stride)       grouped 3x3 conv (pad 1), w [3,3,Cg,C]
+                                                          fp32 (the ResNeXt bottleneck); autograd =
+                                                          the grouped dgrad / wgrad kernels
   torch.ops.cvlite.fcos_assign(boxes, nbox, img_dim, pad_h, pad_w, C)   fcos.format_data, batched
   torch.ops.cvlite.fcos_loss(reg, cls, targets, C, reg_type)  fcos.model_loss per image
                                                           [B, 3] = (cls, reg, cen); autograd = the
@@ -113,6 +116,49 @@ def _conv_backward(ctx, gy):
 
 
 conv2d_nhwc.register_autograd(_conv_backward, setup_context=_conv_setup)
+
+
+# ---- group_conv3x3_nhwc -----------------------------------------------------------------------------
+@torch.library.custom_op("cvlite::group_conv3x3_nhwc", mutates_args=(), device_types="cuda")
+def group_conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, stride: int) -> torch.Tensor:
+    """x [B,H,W,C] bf16 (C % 32 == 0), w [3,3,Cg,C] fp32 (Cg in 4/8/16/32; output channel o reads the
+    input channels of group o // Cg), ZeroPadding2D(1) + valid, stride 1 or 2 -> [B,Ho,Wo,C] bf16."""
+    B, H, W, C = (int(s) for s in x.shape)
+    wf = nn.gconv3x3_packed(C, x.device)
+    nn.gconv3x3_pack(w.contiguous(), wf, None)
+    out = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, C), dtype=BF16, device=x.device)
+    nn.gconv3x3_fwd(x.contiguous(), wf, out, int(w.shape[2]), stride)
+    return out
+
+
+@group_conv3x3_nhwc.register_fake
+def _(x, w, stride):
+    B, H, W, C = x.shape
+    return x.new_empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, C), dtype=BF16)
+
+
+def _gconv_setup(ctx, inputs, output):
+    x, w, stride = inputs
+    ctx.save_for_backward(x, w)
+    ctx.stride = stride
+
+
+def _gconv_backward(ctx, gy):
+    x, w = ctx.saved_tensors
+    g = gy.to(BF16).contiguous()
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        wd = nn.gconv3x3_packed(int(x.shape[3]), x.device)
+        nn.gconv3x3_pack(w.contiguous(), None, wd)
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+        nn.gconv3x3_dgrad(g, wd, dx, int(w.shape[2]), ctx.stride)
+    if ctx.needs_input_grad[1]:
+        dw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x.device)
+        nn.gconv3x3_wgrad(x.contiguous(), g, dw, ctx.stride)
+    return dx, dw, None
+
+
+group_conv3x3_nhwc.register_autograd(_gconv_backward, setup_context=_gconv_setup)
 
 
 # ---- targets ------------------------------------------------------------------------------------

@@ -705,6 +705,40 @@ int cvl_depthwise_wgrad(const void* x, const void* dy, float* dw, float beta, in
                         int stride, int pad_t, int pad_l, int Ho, int Wo, void* workspace, size_t workspace_bytes,
                         cvl_stream_t stream);
 
+/* Grouped 3x3 convolution (the 32-group 3x3 of the ResNeXt bottleneck; the ResNeXt50 / ResNeXt101
+ * branch of RetinaNet/retinanet_module.py:53-66): x [B][H][W][C] bf16, fp32 master kernel
+ * w [3][3][Cg][C] (output channel o is in group o / Cg and reads input channels (o / Cg) * Cg .. + Cg),
+ * y [B][Ho][Wo][C] bf16, ZeroPadding2D(1) + "valid" (pad 1 top / left), Ho = (H - 1) / stride + 1.
+ * C % 32 == 0, Cg in {4, 8, 16, 32}, stride 1 or 2; anything else is CVL_EINVAL.
+ * The kernels read bf16 slab images of the kernel: *_pack writes the forward image and / or the
+ * data-gradient image (either may be null), each *_packed_bytes large
+ * (retinanet_module.py:53-66). */
+size_t cvl_gconv3x3_packed_bytes(int C);
+int cvl_gconv3x3_pack(const float* w, int C, int Cg, void* w_fwd, void* w_dgrad, cvl_stream_t stream);
+/* y = conv(x); bn_stats (or null): BN accumulators [B][C][2][S] of the rounded outputs, added to
+ * (retinanet_module.py:53-66). */
+int cvl_gconv3x3_fwd(const void* x, const void* w_fwd, void* y, uint64_t* bn_stats, int B, int H, int W, int C, int Cg,
+                     int stride, int Ho, int Wo, cvl_stream_t stream);
+/* dx [B][H][W][C] = beta*dx + conv^T(dy [B][Ho][Wo][C]) on the data-gradient image
+ * (retinanet_module.py:53-66). */
+int cvl_gconv3x3_dgrad(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int C, int Cg, int stride,
+                       int Ho, int Wo, float beta, cvl_stream_t stream);
+/* dw [3][3][Cg][C] fp32 = beta*dw + sum over all output pixels of x (x) dy; partial sums reduced in a
+ * fixed order (bit-identical run to run); workspace >= *_size (retinanet_module.py:53-66). */
+size_t cvl_gconv3x3_wgrad_workspace_size(int B, int H, int W, int C, int Cg, int stride);
+int cvl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, float beta, int B, int H, int W, int C, int Cg,
+                       int stride, int Ho, int Wo, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
+
+/* bn_data: the BatchNormalization(scale=False) on the fp32 input image [B][H][W][3] in front of the
+ * ResNeXt stem (retinanet_module.py:53-66).  *_stats: per-image (mean, rstd) [B][3][2] and the
+ * moving-average update of run_mean / run_var [3] (either may be null), deterministic; *_apply:
+ * out = (img - mean) * rstd + beta. */
+size_t cvl_bn_data_stats_workspace_size(int B);
+int cvl_bn_data_stats(const float* img, int B, int H, int W, float eps, float momentum, float* mean_rstd,
+                      float* run_mean, float* run_var, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
+int cvl_bn_data_apply(const float* img, const float* mean_rstd, const float* beta, float* out, int B, int H, int W,
+                      cvl_stream_t stream);
+
 /* CenterNet v2 (CenterNet/tf_hourglass_net.py:115-449, n_filters 12 in train_hourglass_voc.py:298-331)
  * --------------------------------------------------------------------------------------------
  * out = UpSampling2D(bilinear)(a + b) (:252-305; b nullable): taps of a + b in fp32, one pass. */
