@@ -202,6 +202,10 @@ SIGNATURES = {
     "cvl_fcos_detect_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cvl_fcos_detect": (c_int, [P, c_int, P, c_int, c_int, P, P, c_int, c_int, c_float, c_float, c_int, c_int, P, P,
                                 P, P, P, c_size_t, P]),
+    # detection evaluation (include/cvlite.h "Detection evaluation"; cvlite/evaluate.py)
+    "cvl_eval_match": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P,
+                               P, P, ctypes.c_int64, P, P]),
+    "cvl_eval_ap": (c_int, [P, P, P, P, ctypes.c_int64, c_int, c_int, c_int, P, P, P]),
     # JPEG decode (include/cvlite.h "JPEG decode"; cvlite/jpeg.py)
     "cvl_jpeg_info": (c_int, [P, c_size_t, P]),
     "cvl_jpeg_entropy_decode": (c_int, [P, c_size_t, P, c_size_t, P]),

@@ -929,6 +929,69 @@ int cvl_fcos_detect(const float* reg_pred, int ld_reg, const float* cls_pred, in
                     cvl_stream_t stream);
 
 /* ==========================================================================================
+ * Detection evaluation: VOC AP (VOCdevkit VOCevaldet) and COCO-style mAP (pycocotools evaluateImg /
+ * accumulate, area range "all").  The reference has no evaluator; the semantics are
+ * this project's contract (INTEGRATION.md "Evaluation"; numpy restatement tests/eval_ref.py).
+ * Deviations from the two tools: boxes are continuous (no "+1 pixel" of the VOC devkit); recall
+ * levels are compared in integers (a point reaches k / n iff n * tp >= k * npos, no float
+ * linspace); COCO area ranges small / medium / large are not computed.
+ * Both entries need no workspace (the per-image state lives in LDS), launch one kernel, are
+ * stateless and capturable.
+ * ========================================================================================== */
+#define CVL_EVAL_MAX_T 1024          /* detection slots per image */
+#define CVL_EVAL_MAX_G 1024          /* ground-truth slots per image */
+#define CVL_EVAL_MAX_THRESHOLDS 16   /* IoU thresholds K (one bit each in the uint16 bit sets) */
+#define CVL_EVAL_MAX_CLASSES 65535
+#define CVL_EVAL_MAX_B 65535         /* images per call */
+#define CVL_EVAL_AP_CHUNK 1024       /* records per step of cvl_eval_ap's walk over a class segment */
+enum { CVL_EVAL_VOC = 0, CVL_EVAL_COCO = 1 };                            /* matching protocol */
+enum { CVL_EVAL_AP_VOC07 = 0, CVL_EVAL_AP_VOC12 = 1, CVL_EVAL_AP_COCO = 2 }; /* AP mode */
+
+/* Matches one batch.  boxes [B][T][4] fp32 (y1, x1, y2, x2), scores [B][T], classes [B][T] (fp32
+ * class values, as cvl_fcos_detect emits them), valid [B]; gt_boxes [B][G][4], gt_labels [B][G]
+ * int32, gt_flags [B][G] bytes (VOC difficult / COCO iscrowd; NULL = none set), gt_count [B] (all
+ * three may be NULL when G == 0); image_ids [B] int64 in [0, 2^31); thresholds: HOST double [K].
+ * A detection is dropped when its slot >= valid[b], its score is NaN or its class is outside
+ * [0, num_classes); with CVL_EVAL_COCO also when max_dets detections of its (image, class) rank
+ * before it.  Ground truths with a label outside [0, num_classes) are left out.  IoU in float64:
+ * inter / ((ad + ag) - inter), 0 when the denominator <= 0; with CVL_EVAL_COCO against a flagged
+ * (crowd) ground truth inter / ad, 0 when ad <= 0.  Per (image, class) the detections are visited
+ * by score descending, lower slot first among equal scores, separately for each threshold k:
+ *   CVL_EVAL_VOC   jmax = the first ground truth of the class with the strictly largest IoU; IoU >=
+ *                  thr: flagged -> ignored, else unused -> TP (marks it used), else FP; IoU < thr: FP;
+ *   CVL_EVAL_COCO  ground truths non-crowd first, then crowd, each group in the given order; best =
+ *                  min(thr, 1 - 1e-10), m = none; skip a used non-crowd; stop at the crowds when m is
+ *                  set; skip when IoU < best; else best = IoU, m = g (later ties win).  m set: marked
+ *                  used, ignored when m is a crowd, TP otherwise; m unset: FP.
+ * Record i = rec_offset + b * T + t of every slot (the caller provides rec_offset + B * T elements
+ * in each array): rec_score (0 when dropped), rec_class (num_classes when dropped), rec_key =
+ * image_id << 32 | t, rec_tp / rec_ign: bit k = TP / ignored at threshold k.  npos [num_classes]
+ * int32 += the unflagged ground truths per class (integer atomics; the caller zeroes it once).
+ * CVL_EINVAL: B, T, G, K, num_classes outside the limits above (T, K, B, num_classes >= 1, G >= 0),
+ * an unknown protocol, max_dets < 1, rec_offset < 0, a NULL array. */
+int cvl_eval_match(const float* boxes, const float* scores, const float* classes, const int32_t* valid,
+                   const float* gt_boxes, const int32_t* gt_labels, const uint8_t* gt_flags,
+                   const int32_t* gt_count, const int64_t* image_ids, int B, int T, int G, int num_classes,
+                   const double* thresholds /*host[K]*/, int K, int protocol, int max_dets, float* rec_score,
+                   int32_t* rec_class, int64_t* rec_key, uint16_t* rec_tp, uint16_t* rec_ign, int64_t rec_offset,
+                   int32_t* npos, cvl_stream_t stream);
+
+/* AP of every (class, threshold) over n_records records sorted by (class, score descending, key):
+ * rec_tp / rec_ign in that order, seg_offsets [num_classes + 1] int64 (DEVICE) = where each class
+ * starts (the dropped records, class num_classes, sort last), npos as accumulated above.  One
+ * workgroup per (class, threshold) walks its segment in chunks of CVL_EVAL_AP_CHUNK (a segment may
+ * hold many chunks): the TP / FP totals forward, then backward the cumulative counts, precision =
+ * tp / (tp + fp) in float64 and its running maximum from the right (the envelope); ignored records
+ * are skipped.  mode CVL_EVAL_AP_VOC07: the mean over k = 0..10 of the envelope at the first point
+ * with 10 * tp >= k * npos (0 when none); CVL_EVAL_AP_COCO: the same with k = 0..100 and 100;
+ * CVL_EVAL_AP_VOC12: (the sum over the points where tp rises of the envelope) / npos.  ap [K][C]
+ * float64 (NaN where npos == 0, 0 for a class with ground truth and no detections), tp_total [K][C]
+ * int32 = the final TP count.  Deterministic (no floating-point atomics). */
+int cvl_eval_ap(const uint16_t* rec_tp, const uint16_t* rec_ign, const int64_t* seg_offsets, const int32_t* npos,
+                int64_t n_records, int num_classes, int K, int mode, double* ap, int32_t* tp_total,
+                cvl_stream_t stream);
+
+/* ==========================================================================================
  * Input pipeline (FCOS/data_preprocess.py:24-133): resize_and_pad_image + random_flip_horizontal.
  * ========================================================================================== */
 
