@@ -12,6 +12,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxSeg = CVL_CONV_MAX_SEG;
 
+// ReLU of a bf16 value on its bits: sign set -> +0 (exact; the fused residual epilogue and cvl_relu_
+// share it, so the two forms of cvl_conv_igemm_res_relu agree bit for bit)
+__device__ __forceinline__ short relu_bf16_bits(short v) { return v < 0 ? (short)0 : v; }
+
 // kernel variant of the last cvl_conv_igemm call on this host thread (cvl_conv_igemm_last_kernel);
 // the forward / data-gradient family sets it from the launch's ConvPlan (conv_igemm.hip: conv_run)
 extern thread_local int g_cvl_conv_last_kernel;
@@ -154,6 +158,7 @@ struct ConvCallOpts {
   int bsum;                 // fused BN-backward sums offered (CVL_BSUM_*)
   bool ymask;               // a ReLU mask offered (cvl_conv_igemm_relu_mask)
   size_t workspace_bytes;   // 0: no workspace
+  bool res_relu;            // ReLU after the beta accumulate offered (cvl_conv_igemm_res_relu)
 };
 
 enum { CVL_PRE_NONE = 0, CVL_PRE_ZERO_GAPS = 1, CVL_PRE_S2DG3_PACK = 2 };   // pass before the launch
@@ -171,6 +176,7 @@ struct ConvPlan {
   int stages;               // H64 ring stages (2 / 3)
   int bsum;                 // fused BN sums applied (CVL_BSUM_*; NONE when offered but not fusable)
   bool ymask;               // the ReLU mask is applied in the epilogue
+  bool res_relu;            // P: ReLU after the beta accumulate in the epilogue (relu(conv + bias + old))
   int splits, ksteps_per_split;
   int grid;                 // workgroups (per split)
   size_t workspace_bytes;   // workspace this plan uses (pack + split-K slabs)

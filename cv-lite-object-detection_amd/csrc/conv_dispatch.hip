@@ -221,6 +221,8 @@ bool plan_p(const cvl_conv_desc* d, const ConvArgs& a, const ConvCallOpts& o, Co
   p->dbg = cvl_tune_int("CVL_P_ABLATE", 0);
   p->bsum = o.bsum;
   p->acc = a.beta != 0.f && !cvl_tune_flag("CVL_P_NO_ACC");
+  // relu(conv + bias + old) (cvl_conv_igemm_res_relu): the accumulate form's 64- and 128-wide tiles
+  p->res_relu = o.res_relu && p->acc && use != 256 && !cvl_dispatch_flag("no_res_relu_fuse");
   return true;
 }
 

@@ -638,6 +638,60 @@ extern "C" int cvl_conv_igemm_relu_mask(const cvl_conv_desc* d, const void* src,
 }
 
 namespace {
+// what cvl_conv_igemm_res_relu accepts, and its plan (the ReLU after the accumulate offered)
+int res_relu_plan(const cvl_conv_desc* d, size_t ws, ConvPlan* p) {
+  CVL_CHECK_ARG(d && d->mode == CVL_CONV_FWD && d->prec == CVL_PREC_BF16 && !d->dst_f32 && d->beta == 1.f &&
+                !d->relu_out);
+  const int st = conv_plan(d, ConvCallOpts{false, CVL_BSUM_NONE, false, ws, true}, p);
+  if (st) return st;
+  // the separate ReLU pass runs over whole rows from dst
+  if (!p->res_relu) CVL_CHECK_ARG(d->ld_dst == d->n_store && d->dst_coff == 0);
+  return CVL_OK;
+}
+}  // namespace
+
+// A residual unit with its BatchNorm folded into the conv (inference, ResNet50.forward(folded=True):
+// the bottleneck's conv3): dst = relu(conv(src) + bias + dst), forward, bf16, beta 1.  The persistent
+// 1x1 kernel's accumulate form applies the ReLU to the packed value right after the accumulate; any
+// other plan runs the beta = 1 launch followed by the in-place ReLU (then dst must be dense: ld_dst ==
+// n_store, dst_coff 0 -- checked before anything is launched).  ReLU of a bf16 value is exact: the two
+// forms are bit-identical.
+extern "C" int cvl_conv_igemm_res_relu(const cvl_conv_desc* d, const void* src, void* dst, void* workspace,
+                                       size_t workspace_bytes, cvl_stream_t stream) {
+  CVL_CHECK_ARG(src && dst);
+  ConvPlan p;
+  int st = res_relu_plan(d, workspace ? workspace_bytes : 0, &p);
+  if (st) return st;
+  cvl_probe_enter_call();
+  st = conv_run(p, d, ConvIo{src, dst, nullptr, nullptr, nullptr, workspace}, (hipStream_t)stream);
+  cvl_probe_leave_call();
+  if (st || p.res_relu) return st;
+  long lo = d->seg[0].dst_base, hi = 0;      // the rows the segments span
+  for (int i = 0; i < d->nseg; ++i) {
+    const long b = d->seg[i].dst_base;
+    const long e = b + (long)d->B * (d->seg[i].dst_img ? d->seg[i].dst_img : (long)d->seg[i].Hr * d->seg[i].Wr);
+    lo = b < lo ? b : lo;
+    hi = e > hi ? e : hi;
+  }
+  return cvl_relu_(reinterpret_cast<cvl_bf16*>(dst) + lo * d->n_store, (hi - lo) * d->n_store, stream);
+}
+
+// Test and profiling hook: the kernel family a cvl_conv_igemm_res_relu call would use and whether its
+// epilogue applies the ReLU (*fused 1) or the separate pass follows (0).  Host only, no launch.
+extern "C" int cvl_conv_igemm_res_relu_plan(const cvl_conv_desc* d, size_t workspace_bytes, int32_t* kernel,
+                                            int32_t* fused) {
+  CVL_CHECK_ARG(kernel && fused);
+  *kernel = CVL_CK_NONE;
+  *fused = 0;
+  ConvPlan p;
+  const int st = res_relu_plan(d, workspace_bytes, &p);
+  if (st) return st;
+  *kernel = p.kernel;
+  *fused = p.res_relu ? 1 : 0;
+  return CVL_OK;
+}
+
+namespace {
 // The form a fused BN-sums offer ends up with: the offer itself, the y form where only the bitmap
 // form is declined, or CVL_BSUM_NONE.
 int dgrad_bnsum_plan_form(const cvl_conv_desc* d, int offer, size_t ws, int32_t* form) {

@@ -107,7 +107,9 @@ __device__ __forceinline__ unsigned gload1_untracked(const void* p) {
 }
 __device__ __forceinline__ void pin1(unsigned& v) { asm volatile("" : "+v"(v)); }
 
-template <int BN, int BK, bool RELU, bool F32, int BS = 0, bool ACC = false>
+// RRELU (with ACC): ReLU of the stored value, after the beta accumulate -- relu(conv + bias + old), the
+// folded bottleneck's conv3 (cvl_conv_igemm_res_relu)
+template <int BN, int BK, bool RELU, bool F32, int BS = 0, bool ACC = false, bool RRELU = false>
 __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles) {
   using C = PCfg<BN, BK>;
   constexpr int TM = C::TM, TN = C::TN, NS = C::NS, D = C::D;
@@ -426,6 +428,10 @@ __global__ void __launch_bounds__(NT) conv_igemm_p_kernel(ConvArgs a, int ntiles
 #pragma unroll
           for (int u = 0; u < 8; ++u)
             o[u] = (short)f32_to_bf16(bf16_to_f32((cvl_bf16)o[u]) + a.beta * bf16_to_f32((cvl_bf16)old[u]));
+          if (RRELU) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) o[u] = relu_bf16_bits(o[u]);
+          }
         } else if (a.beta != 0.f) {
           const s16x8 old = *pd;
 #pragma unroll
@@ -568,6 +574,8 @@ void p_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     });
   } else if (a.relu_out) {
     hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, true, false>), grid, dim3(NT), 0, s, a, ntiles);
+  } else if (p.acc && p.res_relu) {
+    hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false, 0, ACC_, ACC_>), grid, dim3(NT), 0, s, a, ntiles);
   } else if (p.acc) {
     hipLaunchKernelGGL((conv_igemm_p_kernel<BN_, BK_, false, false, false, ACC_>), grid, dim3(NT), 0, s, a, ntiles);
   } else {

@@ -43,6 +43,10 @@ SIGNATURES = {
     "cvl_conv_igemm_workspace_size": (c_size_t, [P]),
     "cvl_conv_igemm": (c_int, [P, P, P, P, P, c_size_t, P]),
     "cvl_conv_igemm_relu_mask": (c_int, [P, P, P, P, P, c_size_t, P]),
+    "cvl_conv_igemm_res_relu": (c_int, [P, P, P, P, c_size_t, P]),
+    "cvl_conv_igemm_res_relu_plan": (c_int, [P, c_size_t, P, P]),
+    "cvl_pack_conv_weights_scaled_multi": (c_int, [P, P, c_int, P]),
+    "cvl_relu_": (c_int, [P, ctypes.c_long, P]),
     "cvl_conv_igemm_last_kernel": (c_int, []),
     "cvl_conv_igemm_last_ktile": (c_int, []),
     "cvl_conv_igemm_plan": (c_int, [P, c_int, c_size_t, P, P]),
@@ -241,7 +245,8 @@ _lib = None
 NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_plan_bnsum", "cvl_conv_igemm_plan_grid",
          "cvl_conv_igemm_dgrad_bnsum_res_bits", "cvl_bn_finalize_apply_bits", "cvl_bn_finalize_apply_bnres_bits",
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
-         "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan"}
+         "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan", "cvl_conv_igemm_res_relu",
+         "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_"}
 
 
 def load():

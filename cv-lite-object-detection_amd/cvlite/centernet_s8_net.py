@@ -101,19 +101,31 @@ class CenterNetS8Net(object):
                 entries += c.pack_entries()
             self._plan = nn.PackPlan(entries, self.device)
         self._plan.run()
+        self.backbone.fold_fresh = False                # a BN fold (fold_bn) is of the previous weights
+
+    def fold_bn(self):
+        """Fold the backbone's BatchNorms into its convs for inference (ResNet50.fold_bn; MobileNetV2
+        raises NotImplementedError)."""
+        self.backbone.fold_bn()
 
     @staticmethod
     def out_hw(H, W):
         return H // 8, W // 8
 
     # ---- forward / backward -----------------------------------------------------------------
-    def forward(self, x, train=True):
+    def forward(self, x, train=True, folded=False):
         """x [B,H,W,3] fp32 (H, W multiples of 128) -> (reg [B,P,ns*4], cls [B,P,ns*C]) fp32 raw
-        logits, P = (H/8)*(W/8), cell-major then scale."""
+        logits, P = (H/8)*(W/8), cell-major then scale.  folded (inference): the backbone's BNs folded
+        into its convs (fold_bn)."""
         B, H, W, _ = x.shape
         assert H % 128 == 0 and W % 128 == 0, "the P7 -> P3 residual chain needs H, W multiples of 128"
         dev = x.device
-        (C3, C4, C5), bsv = self.backbone.forward(x, train)
+        if folded:
+            if not isinstance(self.backbone, ResNet50):
+                self.backbone.fold_bn()                 # raises NotImplementedError
+            (C3, C4, C5), bsv = self.backbone.forward(x, train, folded=True)
+        else:
+            (C3, C4, C5), bsv = self.backbone.forward(x, train)
         (c3, H3, W3), (c4, H4, W4), (c5, H5, W5) = C3, C4, C5
         l3, _, _ = self.c3_1x1.fwd(c3, B, H3, W3)
         l4, _, _ = self.c4_1x1.fwd(c4, B, H4, W4)

@@ -241,14 +241,16 @@ def _sample_batches(samples, batch_size):
 
 
 def evaluate_fcos(model, samples, num_classes, batch_size=16, protocol="voc07", center=False, iou_thresholds=None,
-                  max_dets=100, **detect_kwargs):
+                  max_dets=100, fold_bn=False, **detect_kwargs):
     """FCOS (cvlite.fcos.build_model or its FCOSNet): infer_fcos.image_detections per batch, then
     Evaluator.add on its device outputs.  detect_kwargs: iou_thresh, cls_thresh, max_detections,
-    max_total_size of image_detections.  Returns Evaluator.result()."""
+    max_total_size of image_detections.  fold_bn: the forwards run with the backbone's BatchNorms
+    folded into its convs (folded once, before the first batch).  Returns Evaluator.result()."""
     from .infer_fcos import image_detections
     ev = Evaluator(num_classes, protocol, iou_thresholds=iou_thresholds, max_dets=max_dets)
     for imgs, gt, ids, real in _sample_batches(samples, batch_size):
-        det = image_detections(torch.from_numpy(imgs).cuda(), model, num_classes, center=center, **detect_kwargs)
+        det = image_detections(torch.from_numpy(imgs).cuda(), model, num_classes, center=center, fold_bn=fold_bn,
+                               **detect_kwargs)
         valid = det.valid_detections.clone()
         valid[real:] = 0
         gtb, gtl, gtc, gtf = (t.cuda() for t in gt)
@@ -264,16 +266,17 @@ def _gt_rows(gt, real):
 
 
 def evaluate_retinanet(retina, samples, num_classes=None, batch_size=16, protocol="coco", iou_thresholds=None,
-                       max_dets=100, iou_thresh=0.5, cls_thresh=0.05):
+                       max_dets=100, iou_thresh=0.5, cls_thresh=0.05, fold_bn=False):
     """RetinaNet (cvlite.retinanet.RetinaNet): inference forward per batch, decode_detections
-    (decode + NMS on the device, rows to the host as that API returns them), Evaluator.add_rows."""
+    (decode + NMS on the device, rows to the host as that API returns them), Evaluator.add_rows.
+    fold_bn: the forwards run with the backbone's BatchNorms folded into its convs."""
     C = retina.n_class if num_classes is None else int(num_classes)
     ev = Evaluator(C, protocol, iou_thresholds=iou_thresholds, max_dets=max_dets)
     net = retina.model
     for imgs, gt, ids, real in _sample_batches(samples, batch_size):
         x = torch.from_numpy(imgs).cuda()
         shapes, _, _ = net.layout(int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
-        reg, cls = net.forward(x, train=False)
+        reg, cls = net.forward(x, train=False, folded=bool(fold_bn))
         rows = retina.decode_detections(reg, cls, shapes, iou_thresh=iou_thresh, cls_thresh=cls_thresh)
         # NMS emits its rows best score first: the slot limit keeps the MAX_T best of an image
         ev.add_rows([r[:MAX_T] for r in rows[:real]], _gt_rows(gt, real), fmt="yxyx", image_ids=ids[:real])

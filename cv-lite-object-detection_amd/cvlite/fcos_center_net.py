@@ -79,6 +79,7 @@ class FCOSCenterNet(FCOSNet):
             entries += [(self._comb[l], 9, FPN_C, ld, FPN_C, ld, None, FPN_C, ld, self._comb_wd[l]) for l in range(5)]
             self._pack_plan = nn.PackPlan(entries, self.device)
         self._pack_plan.run()
+        self.backbone.fold_fresh = False                # a BN fold (fold_bn) is of the previous weights
 
     def _head_launch(self, heads, acts, out, ld, coff, B, shapes, off, P):
         segs = [nn.seg(h, w, h, w, heads[l].wf, heads[l].bias_arg(), src_base=B * off[l], src_img=h * w,

@@ -116,8 +116,15 @@ class FPNDetector(object):
                     entries += c.pack_entries()
             self._pack_plan = nn.PackPlan(entries, self.device)
         self._pack_plan.run()
+        self.backbone.fold_fresh = False                # a BN fold (fold_bn) is of the previous weights
         if isinstance(self.backbone, ResNeXt):          # the grouped 3x3 kernels' slab images
             self.backbone.pack_grouped()
+
+    def fold_bn(self):
+        """Fold the backbone's BatchNorms into its convs for inference (ResNet50.fold_bn; the other
+        backbones raise NotImplementedError).  forward(x, train=False, folded=True) runs on the fold
+        and refreshes a stale one itself."""
+        self.backbone.fold_bn()
 
     # ---- geometry ---------------------------------------------------------------------------------
     @staticmethod
@@ -150,12 +157,18 @@ class FPNDetector(object):
         return segs
 
     # ---- forward -------------------------------------------------------------------------------------
-    def trunk_forward(self, x, train=True):
+    def trunk_forward(self, x, train=True, folded=False):
         """Backbone + FPN + both towers.  Returns the two towers' activation lists (each [F, a1..a4],
-        a4 = ReLU output) over the packed level-major buffer."""
+        a4 = ReLU output) over the packed level-major buffer.  folded (inference): the backbone's BNs
+        folded into its convs (fold_bn)."""
         B, H, W, _ = x.shape
         dev = x.device
-        (C3, C4, C5), bsv = self.backbone.forward(x, train)
+        if folded:
+            if not isinstance(self.backbone, ResNet50):
+                self.backbone.fold_bn()                 # raises NotImplementedError
+            (C3, C4, C5), bsv = self.backbone.forward(x, train, folded=True)
+        else:
+            (C3, C4, C5), bsv = self.backbone.forward(x, train)
         (c3, H3, W3), (c4, H4, W4), (c5, H5, W5) = C3, C4, C5
         # the three 3x3 output convs' sources (P3r, P4r, P5 = l5) share one buffer, so the convs run
         # as ONE 3-segment launch (fcos.py:62-66: same geometry, own weights and biases)
@@ -221,8 +234,8 @@ class FPNDetector(object):
                            tower_bufs=bufs, B=B, H=H, W=W, shapes=shapes, off=off, P=P)
         return towers
 
-    def forward(self, x, train=True):
-        towers = self.trunk_forward(x, train)
+    def forward(self, x, train=True, folded=False):
+        towers = self.trunk_forward(x, train, folded)
         s = self._saved
         return self._heads_forward(towers, s["B"], s["shapes"], s["off"], s["P"])
 

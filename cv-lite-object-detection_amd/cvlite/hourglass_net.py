@@ -425,6 +425,10 @@ class HourglassNet(object):
             out += b.seps()
         return out
 
+    def fold_bn(self):
+        """BN folding for inference (ResNet50.fold_bn) is not provided for this network."""
+        raise NotImplementedError("fold_bn covers the ResNet v1 bottleneck backbones, not the separable hourglass")
+
     def bns(self):
         return [bn for b in self.blocks.values() for bn in b.bns()]
 

@@ -395,6 +395,10 @@ class HourglassV2Net(object):
     def seps(self):
         return [s for b in self.blocks() for s in b.seps()]
 
+    def fold_bn(self):
+        """BN folding for inference (ResNet50.fold_bn) is not provided for this network."""
+        raise NotImplementedError("fold_bn covers the ResNet v1 bottleneck backbones, not the separable hourglass")
+
     def bns(self):
         return [bn for b in self.blocks() for bn in b.bns()]
 

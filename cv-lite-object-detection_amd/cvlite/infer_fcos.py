@@ -50,15 +50,17 @@ def detect_from_outputs(reg, cls, shapes, num_classes, center=False, iou_thresh=
 
 
 def image_detections(image, model, num_classes, center=False, iou_thresh=0.5, cls_thresh=0.05,
-                     max_detections=100, max_total_size=100):
+                     max_detections=100, max_total_size=100, fold_bn=False):
     """infer_fcos.py:27-62.  model = cvlite.fcos.build_model(...) (or its FCOSNet); image
-    [B,H,W,3] / [H,W,3] fp32 (already resized and scaled to [-1, 1])."""
+    [B,H,W,3] / [H,W,3] fp32 (already resized and scaled to [-1, 1]).  fold_bn (cvlite extension): run
+    the forward with the backbone's BatchNorms folded into its convs (FPNDetector.fold_bn; ResNet
+    backbones, bf16) -- the same map up to bf16 rounding, without the BN passes."""
     net = getattr(model, "net", model)
     x = torch.as_tensor(image, dtype=torch.float32, device="cuda")
     if x.dim() == 3:
         x = x.unsqueeze(0)
     B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
     shapes, _, _ = net.layout(B, H, W)
-    reg, cls = net.forward(x.contiguous(), train=False)
+    reg, cls = net.forward(x.contiguous(), train=False, folded=bool(fold_bn))
     return detect_from_outputs(reg, cls, shapes, num_classes, center, iou_thresh, cls_thresh, max_detections,
                                max_total_size)

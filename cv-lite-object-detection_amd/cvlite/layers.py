@@ -476,3 +476,79 @@ class ConvBN(object):
         assert dx_beta == 0.0 or len(bn_next) > 5
         dx = self.conv.dgrad(dz, B, H, W, out=dx_out, beta=dx_beta, bn_next=bn_next)
         return dx
+
+    # ---- inference with the BN folded into the conv ----------------------------------------------------
+    def fold_params(self):
+        """The folded unit's per-channel scale and bias (fold_s, fold_b; FoldPlan.params) -- host or
+        device, wherever the parameters live."""
+        if getattr(self, "_fold_plan", None) is None:
+            self._fold_plan = FoldPlan([self])
+        self._fold_plan.params()
+        return self.fold_s, self.fold_b
+
+    def fold(self):
+        """fold_params + the scaled forward pack wf_fold (one unit; ResNet50.fold_bn folds a whole
+        backbone in one launch)."""
+        if getattr(self, "_fold_plan", None) is None:
+            self._fold_plan = FoldPlan([self])
+        self._fold_plan.run()
+
+    def forward_folded(self, x, B, H, W, relu=True, residual_into=None):
+        """Inference forward of the folded unit: conv (wf_fold, fold_b) with the ReLU in its epilogue.
+        residual_into: the shortcut buffer -- relu(conv + bias + shortcut) is formed in place there
+        (cvl_conv_igemm_res_relu) and returned.  No statistics, nothing saved."""
+        c = self.conv
+        Ho, Wo, _, _ = c.out_hw(H, W)
+        segs = [nn.seg(Ho, Wo, H, W, self.wf_fold, self.fold_b)]
+        if residual_into is not None:
+            assert relu and tuple(residual_into.shape) == (B, Ho, Wo, c.cout)
+            nn.conv_igemm_res_relu(c.fwd_desc(B, segs, ld_dst=c.cout, beta=1.0), x, residual_into)
+            return residual_into, Ho, Wo
+        out = torch.empty((B, Ho, Wo, c.cout), dtype=x.dtype, device=x.device)
+        nn.conv_igemm(c.fwd_desc(B, segs, ld_dst=c.cout, relu_out=relu), x, out)
+        return out, Ho, Wo
+
+
+class FoldPlan(object):
+    """BatchNorm with the moving statistics folded into the convs of a list of ConvBN units (inference):
+    per channel, in float64 from the fp32 masters,
+        s = gamma / sqrt(moving_var + eps),   b' = (b - moving_mean) * s + beta      (b = 0 without a conv bias)
+    both rounded once to fp32 (each unit's fold_s / fold_b are views of one buffer), then every unit's
+    forward pack wf_fold = bf16(w * s[co]) in ONE launch (ops_nn.ScaledPackPlan)."""
+
+    def __init__(self, units):
+        self.units = list(units)
+        st = self.units[0].conv.store
+        if st.act != BF16:
+            raise NotImplementedError("BN folding covers the bf16 production path, not the fp32 parity mode")
+        dev = st.flat.device
+        n = sum(u.bn.c for u in self.units)
+        self.s = torch.empty(n, dtype=torch.float32, device=dev)
+        self.b = torch.empty(n, dtype=torch.float32, device=dev)
+        self.eps = torch.cat([torch.full((u.bn.c,), u.bn.eps, dtype=torch.float64) for u in self.units]).to(dev)
+        o = 0
+        for u in self.units:
+            u.fold_s, u.fold_b = self.s[o:o + u.bn.c], self.b[o:o + u.bn.c]
+            o += u.bn.c
+        self.pack = None
+
+    def params(self):
+        us = self.units
+        cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]).double()
+        gamma, beta = cat([u.bn.gamma for u in us]), cat([u.bn.beta for u in us])
+        mean, var = cat([u.bn.run_mean for u in us]), cat([u.bn.run_var for u in us])
+        bias = cat([u.conv.b if u.conv.has_bias else torch.zeros_like(u.bn.run_mean) for u in us])
+        s = gamma / torch.sqrt(var + self.eps)
+        self.s.copy_(s)
+        self.b.copy_((bias - mean) * s + beta)
+
+    def run(self):
+        self.params()
+        if self.pack is None:
+            entries = []
+            for u in self.units:
+                c = u.conv
+                u.wf_fold = torch.empty((c.npad, c.k * c.k * c.cin_k), dtype=BF16, device=self.s.device)
+                entries.append((c.w, u.fold_s, c.k * c.k, c.cin, c.cout, c.cin_k, c.npad, u.wf_fold))
+            self.pack = nn.ScaledPackPlan(entries, self.s.device)
+        self.pack.run()

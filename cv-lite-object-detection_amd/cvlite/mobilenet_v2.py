@@ -204,6 +204,10 @@ class MobileNetV2(object):
     def convs(self):
         return [None] + [u.conv for b in self.blocks for u in b.units()] + [self.head.conv]
 
+    def fold_bn(self):
+        """BN folding for inference (ResNet50.fold_bn) is not provided for this network."""
+        raise NotImplementedError("fold_bn covers the ResNet v1 bottleneck backbones, not MobileNetV2's ReLU6 units")
+
     def bns(self):
         return [self.stem_bn] + [bn for b in self.blocks for bn in b.bns()]
 

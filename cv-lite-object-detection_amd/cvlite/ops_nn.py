@@ -89,6 +89,34 @@ def conv_igemm_relu_mask(desc, src, dst, y):
               n if ws is not None else 0, stream())
 
 
+def conv_igemm_res_relu(desc, src, dst):
+    """dst = relu(conv(src) + bias + dst) (cvl_conv_igemm_res_relu: a residual unit with its BatchNorm
+    folded into the conv; desc forward, bf16, beta 1, no relu_out).  The persistent 1x1 kernel applies
+    the ReLU after its accumulate; any other plan is followed by the in-place ReLU -- bit-identical."""
+    if src.dtype != BF16 or dst.dtype != BF16:
+        raise NotImplementedError("conv_igemm_res_relu: bf16 only")
+    desc.prec = PREC_BF16
+    n = int(_lib.load().cvl_conv_igemm_workspace_size(ctypes.byref(desc)))
+    ws = torch.empty(n, dtype=torch.uint8, device=src.device) if n > 16 else None
+    _lib.call("cvl_conv_igemm_res_relu", ctypes.byref(desc), ptr(src), ptr(dst), ptr(ws),
+              n if ws is not None else 0, stream())
+
+
+def conv_igemm_res_relu_plan(desc, workspace_bytes=0):
+    """(kernel family code, fused 0 / 1) of a conv_igemm_res_relu call (host only, no launch)."""
+    k, f = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    _lib.call("cvl_conv_igemm_res_relu_plan", ctypes.byref(desc), int(workspace_bytes), ctypes.byref(k),
+              ctypes.byref(f))
+    return k.value, f.value
+
+
+def relu_(x):
+    """In-place ReLU of a contiguous bf16 tensor (cvl_relu_)."""
+    assert x.dtype == BF16 and x.is_contiguous()
+    _lib.call("cvl_relu_", ptr(x), x.numel(), stream())
+    return x
+
+
 def probe_arm(slot):
     """Time the next conv_igemm launch from inside if it runs the tower kernel (slot: uint64 [4]
     device tensor, zeroed; cvl_probe_arm)."""
@@ -221,6 +249,37 @@ class PackPlan(object):
 
     def run(self):
         _lib.call("cvl_pack_conv_weights_multi", ptr(self.items), ptr(self.tiles), self.ntiles, stream())
+
+
+class PackScaledItem(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("scale", c_void_p), ("w_fwd", c_void_p), ("KHW", c_int), ("Cin", c_int),
+                ("Cout", c_int), ("Cin_k", c_int), ("Npad", c_int)]
+
+
+class ScaledPackPlan(object):
+    """Device tables for cvl_pack_conv_weights_scaled_multi: the forward packs of several convs with a
+    per-output-channel scale (BatchNorm folded into the weights) in one launch.
+    entries: (w_hwio fp32, scale fp32 [Cout], KHW, Cin, Cout, Cin_k, Npad, w_fwd bf16)."""
+
+    def __init__(self, entries, device):
+        items = (PackScaledItem * len(entries))()
+        tiles = []
+        self._keep = []
+        for i, (w, scale, khw, cin, cout, cin_k, npad, wf) in enumerate(entries):
+            assert cin_k % 8 == 0 and cin_k >= cin and npad >= cout and wf.dtype == BF16
+            assert scale.dtype == torch.float32 and scale.numel() == cout and wf.numel() == npad * khw * cin_k
+            it = items[i]
+            it.w, it.scale, it.w_fwd = w.data_ptr(), scale.data_ptr(), wf.data_ptr()
+            it.KHW, it.Cin, it.Cout, it.Cin_k, it.Npad = khw, cin, cout, cin_k, npad
+            self._keep.append((w, scale, wf))
+            tiles += [(i, tap, ci0, co0) for tap in range(khw) for ci0 in range(0, cin_k, 64)
+                      for co0 in range(0, npad, 64)]
+        self.items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(device)
+        self.tiles = torch.tensor(tiles, dtype=torch.int32, device=device)
+        self.ntiles = len(tiles)
+
+    def run(self):
+        _lib.call("cvl_pack_conv_weights_scaled_multi", ptr(self.items), ptr(self.tiles), self.ntiles, stream())
 
 
 def stem_conv7x7s2(img, w_packed, bias, z, stats=None):

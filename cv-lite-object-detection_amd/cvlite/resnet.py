@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import ops_nn as nn
-from .layers import BF16, FUSE_SC_BNSUM, BatchNorm, Conv, ConvBN, StatsArena, wgrad_batch
+from .layers import BF16, FUSE_SC_BNSUM, BatchNorm, Conv, ConvBN, FoldPlan, StatsArena, wgrad_batch
 from . import _lib
 
 STEM_K = 7
@@ -147,6 +147,19 @@ class Bottleneck(object):
         y3, sv3 = self.c3.forward(y2, B, H1, W1, relu=True, residual=s, train=train, arena=arena, residual_bn=s_bn)
         return y3, H1, W1, (sv_s, sv1, sv2, sv3)
 
+    def forward_folded(self, x, B, H, W):
+        """Inference with the BNs folded into the convs (ResNet50.fold_bn).  A projection block writes
+        S = sc'(x) and leaves x as it is; an identity block forms its output IN its input buffer x:
+        relu(c3'(.) + bias + shortcut) accumulates into the shortcut (cvl_conv_igemm_res_relu), and
+        nothing reads a block's input after its conv1."""
+        s = x
+        if self.sc is not None:
+            s, _, _ = self.sc.forward_folded(x, B, H, W, relu=False)
+        y1, H1, W1 = self.c1.forward_folded(x, B, H, W)
+        y2, _, _ = self.c2.forward_folded(y1, B, H1, W1)
+        y3, _, _ = self.c3.forward_folded(y2, B, H1, W1, residual_into=s)
+        return y3, H1, W1
+
     def backward(self, dy, saved, dx_out=None, dx_beta=0.0, arena=None, sums3=None, prev_ctx=None):
         """Returns (dx, sums of the previous block's conv3 BN or None).  sums3: this block's conv3 BN
         first pass, formed by the next block's conv1 data gradient (skipped here); prev_ctx: the
@@ -214,6 +227,8 @@ class ResNet50(object):
                                         stride if bi == 0 else 1, bi == 0))
                 cin = 4 * f
             self.stages.append(stage)
+        self._fold = None
+        self.fold_fresh = False
 
     def convs(self):
         out = [self.stem.conv]
@@ -242,10 +257,39 @@ class ResNet50(object):
             for b in st:
                 for u in b.units():
                     u.conv.pack()
+        self.fold_fresh = False
 
-    def forward(self, x, train=True):
-        """x: fp32 NHWC [B,H,W,3] in [-1,1].  Returns [C3, C4, C5] bf16 NHWC and saved state."""
+    def fold_bn(self):
+        """Fold every bottleneck unit's BatchNorm (moving statistics) into its conv for inference:
+        per-channel scale into a second forward pack, shift into the bias, all units in one launch
+        (layers.FoldPlan).  The stem keeps its fused BN + ReLU + pool pass.  A re-pack of the weights
+        (every optimizer step, a checkpoint load) or a training forward marks the fold stale;
+        forward(folded=True) then folds again first."""
+        if self._fold is None:
+            self._fold = FoldPlan([u for st in self.stages for b in st for u in b.units()])
+        self._fold.run()
+        self.fold_fresh = True
+
+    def forward(self, x, train=True, folded=False):
+        """x: fp32 NHWC [B,H,W,3] in [-1,1].  Returns [C3, C4, C5] bf16 NHWC and saved state.
+        folded (inference only): the bottleneck BNs folded into the convs (fold_bn) -- no statistics,
+        no BN pass, nothing saved (saved state None)."""
         B = x.shape[0]
+        if folded:
+            if train:
+                raise ValueError("folded=True is an inference forward (train=False)")
+            if not self.fold_fresh:
+                self.fold_bn()
+            h, _ = self.stem.forward(x, False, None)
+            H, W = h.shape[1], h.shape[2]
+            taps = []
+            for st in self.stages:
+                for b in st:
+                    h, H, W = b.forward_folded(h, B, H, W)
+                taps.append((h, H, W))
+            return taps[1:], None
+        if train:
+            self.fold_fresh = False         # the moving statistics move
         # forward BN statistics + (second half) the backward's fused first-pass sums: one memset
         arena = StatsArena(4 * B * sum(bn.c for bn in self.bns()), x.device)
         h, sv_stem = self.stem.forward(x, train, arena)

@@ -252,6 +252,10 @@ class ResNeXt(object):
     def gconvs(self):
         return [b.g for b in self.blocks()]
 
+    def fold_bn(self):
+        """BN folding for inference (ResNet50.fold_bn) is not provided for this network."""
+        raise NotImplementedError("fold_bn covers the ResNet v1 bottleneck backbones, not ResNeXt's grouped 3x3 units")
+
     def bns(self):
         return [self.stem.bn_data, self.stem.bn] + [bn for b in self.blocks() for bn in b.bns()]
 

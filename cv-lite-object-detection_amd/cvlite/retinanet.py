@@ -211,14 +211,15 @@ class RetinaNet(object):
                 out.append(dets[b][keep_h[b, :int(nk_h[b])].long().cuda()].cpu().numpy())
         return out
 
-    def image_detections(self, image, iou_thresh=0.5, cls_thresh=0.05):
+    def image_detections(self, image, iou_thresh=0.5, cls_thresh=0.05, fold_bn=False):
         """retinanet_module.py:483-529: inference forward (BN running statistics), decode, NMS ->
-        fp32 [k,6] (y1, x1, y2, x2, score, class) for image [1,H,W,3] (or [H,W,3])."""
+        fp32 [k,6] (y1, x1, y2, x2, score, class) for image [1,H,W,3] (or [H,W,3]).  fold_bn (cvlite
+        extension): the backbone's BatchNorms folded into its convs (FPNDetector.fold_bn)."""
         net = self.model
         x = torch.as_tensor(image, dtype=torch.float32, device="cuda")
         if x.dim() == 3:
             x = x.unsqueeze(0)
         B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
         shapes, _, _ = net.layout(B, H, W)
-        reg, cls = net.forward(x.contiguous(), train=False)
+        reg, cls = net.forward(x.contiguous(), train=False, folded=bool(fold_bn))
         return self.decode_detections(reg, cls, shapes, iou_thresh, cls_thresh)[0]

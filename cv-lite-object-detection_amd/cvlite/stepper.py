@@ -87,7 +87,15 @@ class GraphStepper(object):
                 g.replay()
         else:
             self._fwd_bwd(None)
+        self._fold_stale()
         return self.losses
+
+    def _fold_stale(self):
+        """A replayed step moves the weights and the BN moving statistics without passing through the
+        Python side of pack(): a backbone's BN fold (ResNet50.fold_bn) is stale after it."""
+        bb = getattr(self.net, "backbone", None)
+        if bb is not None:
+            bb.fold_fresh = False
 
     def invalidate(self):
         self.segs = None
@@ -109,4 +117,5 @@ class GraphStepper(object):
             self.g_up.replay()
         else:
             self._update()
+        self._fold_stale()
         return self.losses

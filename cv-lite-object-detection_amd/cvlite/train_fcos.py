@@ -343,7 +343,8 @@ def _batch_from_samples(train_data, idx, n_max):
 def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_manager, st_step, max_steps,
           init_lr=1.0e-3, min_lr=1.0e-5, decay_step=1000, decay_rate=0.99, display_step=50, step_save=100,
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
-          max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07"):
+          max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07",
+          eval_fold_bn=False):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -372,7 +373,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       decodes each batch's files in one cvlite.jpeg.decode_batch call (the same pixels).
     * eval_data / eval_every / eval_protocol (cvlite extension, off by default): pre-processed
       samples of one padded size (optionally with `difficult`); every eval_every steps rank 0 runs
-      cvlite.evaluate.evaluate_fcos over them and prints one "Eval mAP:" line.
+      cvlite.evaluate.evaluate_fcos over them and prints one "Eval mAP:" line; eval_fold_bn runs those
+      forwards with the backbone's BatchNorms folded into its convs (evaluate_fcos(fold_bn=True)).
     The reference's thermal "Cooling GPU" sleep runs only with CVL_COOLING=1.  Returns None."""
     from . import checkpoint as ck
     import torch.distributed as tdist
@@ -479,7 +481,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
                 say("-" * 50)
         if eval_data is not None and eval_every > 0 and (step + 1) % eval_every == 0 and rank == 0:
             from .evaluate import evaluate_fcos
-            res = evaluate_fcos(net, eval_data, net.C, batch_size=batch_size, protocol=eval_protocol)
+            res = evaluate_fcos(net, eval_data, net.C, batch_size=batch_size, protocol=eval_protocol,
+                                fold_bn=eval_fold_bn)
             say("Eval mAP:", str(res["mAP"]))
         if (step + 1) % step_cool == 0:
             say("Trend Loss:", str(round(trend_loss / step_cool, 5)))

@@ -189,6 +189,19 @@ int cvl_conv_igemm(const cvl_conv_desc* d, const void* src, void* dst, uint64_t*
  * must be dense: ld_dst == n_store, dst_coff 0).  Bit-identical to cvl_conv_igemm + cvl_relu_backward. */
 int cvl_conv_igemm_relu_mask(const cvl_conv_desc* d, const void* src, void* dst, const void* y, void* workspace,
                              size_t workspace_bytes, cvl_stream_t stream);
+/* A residual unit whose BatchNorm is folded into the conv (inference; no reference counterpart: Keras
+ * runs conv, BN, Add, ReLU as four ops): dst = relu(conv(src) + bias + dst), mode CVL_CONV_FWD, prec bf16,
+ * beta 1, no relu_out, bf16 dst.  Where the plan is the persistent 1x1 kernel's accumulate form (64- /
+ * 128-wide tiles) its epilogue applies the ReLU right after the accumulate; any other plan runs the
+ * beta = 1 launch followed by cvl_relu_ over the destination rows (then dst must be dense: ld_dst ==
+ * n_store, dst_coff 0 -- checked before anything is launched; CVL_DISPATCH=no_res_relu_fuse forces this
+ * form).  ReLU of a bf16 value is exact: the two forms are bit-identical.  dst may not alias src. */
+int cvl_conv_igemm_res_relu(const cvl_conv_desc* d, const void* src, void* dst, void* workspace,
+                            size_t workspace_bytes, cvl_stream_t stream);
+/* Test and profiling hook, as cvl_conv_igemm_plan: the kernel family (*kernel) a cvl_conv_igemm_res_relu
+ * call would use and whether its epilogue applies the ReLU (*fused = 1) or the separate pass follows
+ * (0).  Host only, no launch.  CVL_EINVAL where the call would reject d. */
+int cvl_conv_igemm_res_relu_plan(const cvl_conv_desc* d, size_t workspace_bytes, int32_t* kernel, int32_t* fused);
 
 /* Test / profiling hook: the kernel variant the last cvl_conv_igemm / cvl_conv_wgrad* call on THIS
  * host thread launched.  CVL_CK_* codes; cvl_conv_kernel_name(code) is a static string.  Codes 6
@@ -295,6 +308,18 @@ typedef struct {
 } cvl_pack_item;
 int cvl_pack_conv_weights_multi(const cvl_pack_item* items, const int32_t* tiles, int ntiles,
                                 cvl_stream_t stream);
+/* The batched forward re-pack with a per-output-channel scale (BatchNorm folded into the conv for
+ * inference, ConvBN.fold): w_fwd[co][tap * Cin_k + ci] = bf16_rne(w[tap][ci][co] * scale[co]) (one fp32
+ * multiply), zero rows >= Cout and channels >= Cin.  Forward pack only.  tiles as above, covering
+ * ci < Cin_k and co < Npad; Cin_k % 8 == 0. */
+typedef struct {
+  const float* w;      /* HWIO fp32 master [KH*KW][Cin][Cout] */
+  const float* scale;  /* fp32 [Cout] */
+  void* w_fwd;         /* bf16 [Npad][KHW*Cin_k] */
+  int KHW, Cin, Cout, Cin_k, Npad;
+} cvl_pack_scaled_item;
+int cvl_pack_conv_weights_scaled_multi(const cvl_pack_scaled_item* items, const int32_t* tiles, int ntiles,
+                                       cvl_stream_t stream);
 
 /* ResNet stem straight from the image (Keras ResNet50 conv1: ZeroPadding2D(3) + Conv2D(64, 7,
  * strides=2) + bias, behind FCOS/fcos.py:30-46 and RetinaNet/retinanet_module.py:39-72; no im2col
@@ -496,6 +521,8 @@ int cvl_upsample2x_add(const void* a, const void* b, void* out, int B, int H, in
 int cvl_upsample2x_backward(const void* dout, void* db, int B, int H, int W, int C, float beta,
                             cvl_stream_t stream);
 int cvl_relu_backward(const void* dy, const void* y, void* dx, long n, float beta, cvl_stream_t stream);
+/* In-place ReLU of n bf16 values (16-byte vectors, any n). */
+int cvl_relu_(void* x, long n, cvl_stream_t stream);
 int cvl_add(const void* a, const void* b, void* out, long n, cvl_stream_t stream);
 /* bias gradient over a segment's rows: db[c] = beta*db + sum dy[row][coff + c] (rows base +
  * b*img_stride + q, q < HW); deterministic (per-block partials summed in a fixed order).  Needs
