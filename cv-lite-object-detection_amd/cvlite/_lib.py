@@ -210,6 +210,9 @@ SIGNATURES = {
     "cvl_eval_match": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P,
                                P, P, ctypes.c_int64, P, P]),
     "cvl_eval_ap": (c_int, [P, P, P, P, ctypes.c_int64, c_int, c_int, c_int, P, P, P]),
+    "cvl_eval_match_areas": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int,
+                                     P, c_int, P, P, P, P, P, P, P, P, ctypes.c_int64, P, P]),
+    "cvl_eval_ap_views": (c_int, [P, P, P, P, P, ctypes.c_int64, c_int, c_int, c_int, P, c_int, P, P, P]),
     # JPEG decode (include/cvlite.h "JPEG decode"; cvlite/jpeg.py)
     "cvl_jpeg_info": (c_int, [P, c_size_t, P]),
     "cvl_jpeg_entropy_decode": (c_int, [P, c_size_t, P, c_size_t, P]),
@@ -246,7 +249,8 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_conv_igemm_dgrad_bnsum_res_bits", "cvl_bn_finalize_apply_bits", "cvl_bn_finalize_apply_bnres_bits",
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
          "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan", "cvl_conv_igemm_res_relu",
-         "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_"}
+         "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_", "cvl_eval_match_areas",
+         "cvl_eval_ap_views"}
 
 
 def load():

@@ -961,8 +961,10 @@ int cvl_fcos_detect(const float* reg_pred, int ld_reg, const float* cls_pred, in
  * this project's contract (INTEGRATION.md "Evaluation"; numpy restatement tests/eval_ref.py).
  * Deviations from the two tools: boxes are continuous (no "+1 pixel" of the VOC devkit); recall
  * levels are compared in integers (a point reaches k / n iff n * tp >= k * npos, no float
- * linspace); COCO area ranges small / medium / large are not computed.
- * Both entries need no workspace (the per-image state lives in LDS), launch one kernel, are
+ * linspace); cvl_eval_match / cvl_eval_ap score COCO's area range "all" at one max_dets, and
+ * cvl_eval_match_areas / cvl_eval_ap_views add the small / medium / large ranges and AR@1/10/100
+ * (there "all" is unbounded, not [0, 1e10], and areas are box areas unless gt_area is given).
+ * Every entry needs no workspace (the per-image state lives in LDS), launches one kernel, is
  * stateless and capturable.
  * ========================================================================================== */
 #define CVL_EVAL_MAX_T 1024          /* detection slots per image */
@@ -1017,6 +1019,62 @@ int cvl_eval_match(const float* boxes, const float* scores, const float* classes
 int cvl_eval_ap(const uint16_t* rec_tp, const uint16_t* rec_ign, const int64_t* seg_offsets, const int32_t* npos,
                 int64_t n_records, int num_classes, int K, int mode, double* ap, int32_t* tp_total,
                 cvl_stream_t stream);
+
+/* ---- COCO area ranges and detection-count views (pycocotools evaluateImg per areaRng, accumulate
+ * per maxDets): the twelve-number summary AP, AP50, AP75, APs, APm, APl, AR@1, AR@10, AR@100, ARs,
+ * ARm, ARl.  Two entries beside the two above, which are unchanged. ---- */
+#define CVL_EVAL_MAX_AREAS 4         /* area ranges A per cvl_eval_match_areas call */
+#define CVL_EVAL_MAX_VIEWS 8         /* (area index, max_rank) views R per cvl_eval_ap_views call */
+
+/* cvl_eval_match under CVL_EVAL_COCO (the only protocol; another one is CVL_EINVAL), once per area
+ * range a < A (1 <= A <= CVL_EVAL_MAX_AREAS): the inputs, the dropping, the ranking, the max_dets
+ * cut per (image, class) -- one cut, the same for every range -- and the IoU arithmetic are
+ * cvl_eval_match's.  area_ranges: HOST double [A][2] = (lo, hi); a value v is outside range a iff
+ * v < lo || v > hi (both ends inclusive, as pycocotools: an area of exactly 1024 is small and
+ * medium; -inf / +inf leave a side open).  Areas in float64: a detection's is (y2 - y1) * (x2 - x1)
+ * from its fp32 corners; a ground truth's is the same expression on its box, or (double)
+ * gt_area[b][g] when gt_area [B][G] is not NULL (COCO's `area` is the mask area).  area_scale [B]
+ * (NULL = none): every box-derived area is multiplied once by (double)area_scale[b] -- original
+ * pixels^2 per network pixel^2 when the boxes live on a resized input; a supplied gt_area is used
+ * as is.  Per range a and threshold k, with their own used flags:
+ *   ign_a[g] = crowd[g] || area_g outside a; the class's ground truths are visited not-ignored
+ *   first, then ignored, each group in the given order; npos[a][c] += the ground truths with !ign_a.
+ *   Per detection in rank order: best = min(thr, 1 - 1e-10), m = none; per g in that order: skip
+ *   when used[g] && !crowd[g]; stop when m is set, !ign_a[m] and ign_a[g]; IoU in the crowd form iff
+ *   crowd[g]; skip when IoU < best; else best = IoU, m = g (later ties win).  m set: used[m] = 1,
+ *   the detection is ignored iff ign_a[m], else a TP.  m unset: ignored iff the detection's own area
+ *   is outside a, else an FP.
+ * With A = 1 and the range (-inf, +inf) the records equal cvl_eval_match's bit for bit.
+ * Outputs at record i = rec_offset + b * T + t (rec_offset counts records): rec_score / rec_class /
+ * rec_key as cvl_eval_match; rec_tp / rec_ign [n][A] uint16, record-major (element i * A + a: bit k
+ * = TP / ignored at threshold k in range a); rec_rank [n] uint16 = the detection's rank inside its
+ * (image, class), counted before the max_dets cut (0xffff for every dropped slot, those the cut
+ * drops included); npos [A][num_classes] int32 += (integer atomics).
+ * One workgroup per image, one launch, all state in LDS (63 KiB at T = G = 1024, K = 16, A = 4: one
+ * lane per (class present, threshold) walks the ranges serially, the range bits of a ground truth
+ * share its used byte), no workspace.  CVL_EINVAL: as cvl_eval_match, and a protocol other than
+ * CVL_EVAL_COCO, A outside [1, 4], area_ranges or rec_rank NULL. */
+int cvl_eval_match_areas(const float* boxes, const float* scores, const float* classes, const int32_t* valid,
+                         const float* gt_boxes, const int32_t* gt_labels, const uint8_t* gt_flags,
+                         const int32_t* gt_count, const int64_t* image_ids, int B, int T, int G, int num_classes,
+                         const double* thresholds /*host[K]*/, int K, int protocol, int max_dets,
+                         const double* area_ranges /*host[A][2]*/, int A, const float* gt_area /*[B][G] or NULL*/,
+                         const float* area_scale /*[B] or NULL*/, float* rec_score, int32_t* rec_class,
+                         int64_t* rec_key, uint16_t* rec_tp, uint16_t* rec_ign, uint16_t* rec_rank,
+                         int64_t rec_offset, int32_t* npos, cvl_stream_t stream);
+
+/* cvl_eval_ap in mode CVL_EVAL_AP_COCO over R views of the same sorted records, one launch with
+ * grid (class, threshold, view): views HOST int32 [R][2] = (area index a in [0, A), max_rank >= 1),
+ * 1 <= R <= CVL_EVAL_MAX_VIEWS.  View r walks bit k of rec_tp / rec_ign [n][A] at element i * A + a
+ * against npos[a][c]; a record is skipped when its ignored bit is set or rec_rank[i] >= max_rank
+ * (matching is greedy in rank order, so a rank prefix is pycocotools' maxDets slice).  ap
+ * [R][K][C] float64 (NaN where npos[a][c] == 0), tp_total [R][K][C] int32.  Same walk and fixed-
+ * order block reductions as cvl_eval_ap.  CVL_EINVAL: the limits of cvl_eval_ap, A outside [1, 4],
+ * R outside [1, 8], a view with an area index outside [0, A) or max_rank < 1, a NULL array. */
+int cvl_eval_ap_views(const uint16_t* rec_tp, const uint16_t* rec_ign, const uint16_t* rec_rank,
+                      const int64_t* seg_offsets, const int32_t* npos, int64_t n_records, int num_classes, int K,
+                      int A, const int32_t* views /*host[R][2]*/, int R, double* ap, int32_t* tp_total,
+                      cvl_stream_t stream);
 
 /* ==========================================================================================
  * Input pipeline (FCOS/data_preprocess.py:24-133): resize_and_pad_image + random_flip_horizontal.

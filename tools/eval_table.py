@@ -10,7 +10,11 @@ beside in an evaluation pass and what it replaces:
 Records the ratios (a) / (d) and ((a) x batches + (b)) / (c); there is no threshold.  (a), (b), (d):
 warm-up passes first, then the median of --reps timed passes.  The device result is also compared
 with the restatement's (max |ap - ref|), so the times are of code that computes the same thing.
-usage: eval_table.py [--images 5000] [--reps 5] [--protocol coco] [--out profiles/eval_table.md]"""
+--area-ranges coco also times an Evaluator(area_ranges="coco") (cvl_eval_match_areas per batch,
+cvl_eval_ap_views in result(): the small / medium / large ranges and AR@1 / 10 / 100) on the same
+batches, its passes alternating with the unranged evaluator's, and compares all its views with
+tests/eval_area_ref.evaluate: rows (a'), (b'), (c').
+usage: eval_table.py [--images 5000] [--reps 5] [--protocol coco] [--area-ranges coco] [--out profiles/eval_table.md]"""
 import argparse
 import os
 import statistics
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--images", type=int, default=5000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--protocol", default="coco")
+    ap.add_argument("--area-ranges", default=None, choices=["coco"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -69,29 +74,33 @@ def main():
         sl = slice(i0, min(n, i0 + BS))
         b, s, c, v, gb, gl, gf, gc = (torch.from_numpy(np.ascontiguousarray(a[sl])).cuda() for a in data)
         batches.append((b, s, c, v, gb, gl, gc, gf, torch.arange(sl.start, sl.stop, dtype=torch.int64, device="cuda")))
-    ev = Evaluator(C, args.protocol, capacity=n * T)
+    evs = [Evaluator(C, args.protocol, capacity=n * T)]
+    if args.area_ranges:
+        evs.append(Evaluator(C, args.protocol, capacity=n * T, area_ranges=args.area_ranges))
 
-    def one_pass():
+    def one_pass(ev):
         ev.reset()
         for b, s, c, v, gb, gl, gc, gf, ids in batches:
             ev.add(b, s, c, v, gb, gl, gc, gt_flags=gf, image_ids=ids)
 
     for _ in range(2):
-        one_pass()
-        res = ev.result()
-    t_add, t_res = [], []
+        for ev in evs:
+            one_pass(ev)
+            ev.result()
+    t_add, t_res, results = [[] for _ in evs], [[] for _ in evs], [None] * len(evs)
     for _ in range(args.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        one_pass()
-        e1.record()
-        torch.cuda.synchronize()
-        t_add.append(e0.elapsed_time(e1) / len(batches))
-        h0 = time.perf_counter()
-        res = ev.result()
-        t_res.append((time.perf_counter() - h0) * 1e3)
-    a_ms, b_ms = statistics.median(t_add), statistics.median(t_res)
+        for i, ev in enumerate(evs):                 # the configurations alternate
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            one_pass(ev)
+            e1.record()
+            torch.cuda.synchronize()
+            t_add[i].append(e0.elapsed_time(e1) / len(batches))
+            h0 = time.perf_counter()
+            results[i] = ev.result()
+            t_res[i].append((time.perf_counter() - h0) * 1e3)
+    a_ms, b_ms, res = statistics.median(t_add[0]), statistics.median(t_res[0]), results[0]
 
     images = [dict(id=i, boxes=data[0][i], scores=data[1][i], classes=data[2][i], valid=int(data[3][i]),
                    gt_boxes=data[4][i], gt_labels=data[5][i], gt_flags=data[6][i], gt_count=int(data[7][i]))
@@ -100,6 +109,15 @@ def main():
     ref = eval_ref.evaluate(images, C, args.protocol)
     c_ms = (time.perf_counter() - h0) * 1e3
     err = float(np.nanmax(np.abs(res["ap"] - ref["ap"])))
+    if args.area_ranges:
+        import eval_area_ref
+        a2_ms, b2_ms, res2 = statistics.median(t_add[1]), statistics.median(t_res[1]), results[1]
+        h0 = time.perf_counter()
+        ref2 = eval_area_ref.evaluate(images, C)
+        c2_ms = (time.perf_counter() - h0) * 1e3
+        err2 = float(np.nanmax(np.abs(res2["ap_area"] - ref2["ap"][:4])))
+        err_s = max(abs(g - r) for g, r in zip(res2["summary"], ref2["summary"]) if r == r)
+        same = res2["ap"].tobytes() == res["ap"].tobytes()
 
     model = fcos.build_model(20)
     x = (torch.rand((BS, 512, 512, 3)) * 2 - 1).cuda()
@@ -122,7 +140,8 @@ def main():
         "Device-resident evaluation on a synthetic validation set: %d images x %d detections, %d classes, %.1f ground "
         "truths per image, protocol %s, %s; median of %d passes." % (
             n, T, C, float(data[7].mean()), args.protocol, torch.cuda.get_device_name(0), args.reps),
-        "Command: `python tools/eval_table.py --images %d --reps %d --protocol %s`" % (n, args.reps, args.protocol), "",
+        "Command: `python tools/eval_table.py --images %d --reps %d --protocol %s%s`" % (
+            n, args.reps, args.protocol, " --area-ranges coco" if args.area_ranges else ""), "",
         "| | what | time |", "|---|---|---|",
         "| (a) | Evaluator.add, per batch of %d (%d batches per pass; HIP events, launch gaps included) | %.3f ms |" % (
             BS, len(batches), a_ms),
@@ -133,6 +152,21 @@ def main():
         "", "(a) / (d) = %.4f" % (a_ms / d_ms),
         "((a) x batches + (b)) / (c) = %.5f  (%.1f ms against %.0f ms)" % (total / c_ms, total, c_ms),
         "mAP %.6f; max |ap - restatement| = %.3g over the %d x %d table." % (res["mAP"], err, len(res["thresholds"]), C)]
+    if args.area_ranges:
+        total2 = a2_ms * len(batches) + b2_ms
+        lines += [
+            "", "With `--area-ranges coco` (Evaluator(area_ranges=\"coco\"): four ranges, six views), same batches, passes "
+            "alternating with the unranged evaluator's:", "", "| | what | time |", "|---|---|---|",
+            "| (a') | Evaluator.add (cvl_eval_match_areas), per batch of %d | %.3f ms |" % (BS, a2_ms),
+            "| (b') | Evaluator.result() (3 stable sorts + cvl_eval_ap_views + copy to host; host clock) | %.2f ms |" % b2_ms,
+            "| (c') | numpy restatement tests/eval_area_ref.evaluate, same data (host clock, one run) | %.0f ms |" % c2_ms,
+            "", "(a') / (a) = %.2f; (a') / (d) = %.4f" % (a2_ms / a_ms, a2_ms / d_ms),
+            "((a') x batches + (b')) / (c') = %.5f  (%.1f ms against %.0f ms)" % (total2 / c2_ms, total2, c2_ms),
+            "max |ap_area - restatement| = %.3g over the 4 x %d x %d table; max |summary - restatement| = %.3g; "
+            "ap of range \"all\" bitwise equal to the unranged evaluator's: %s." % (
+                err2, len(res2["thresholds"]), C, err_s, same),
+            "summary (AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl): " +
+            " ".join("%.4f" % v for v in res2["summary"])]
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
