@@ -19,6 +19,7 @@
 // predictions and targets once and writes the gradients once (HBM-bound); per-image sums are
 // reduced deterministically (per-tile partials in float64, then a fixed-order second pass).
 #include "cvl_common.h"
+#include "fcos_focal.h"
 
 namespace {
 
@@ -53,25 +54,7 @@ __device__ __forceinline__ float sl1(float d, float delta, float* g) {
   return ad;
 }
 
-// q^gamma: the reference default gamma = 2 as a product (the values every training path uses)
-__device__ __forceinline__ float powg(float q, float gamma) { return gamma == 2.0f ? q * q : powf(q, gamma); }
-
-// focal loss term (the reference's stable form, fcos.py:443-462) and d/dx:
-//   y a q^g (L - min(x,0)) + (1-y)(1-a) p^g (L + max(x,0)),  p = sigmoid(x), q = 1 - p, L = log(1+e^-|x|)
-//   d/dx = -y a q^g (g p nlp + q) + (1-y)(1-a) p^g (g q nlq + p)
-__device__ __forceinline__ float focal_term(float y, float x, float alpha, float gamma, float* g) {
-  const float e = expf(-fabsf(x));
-  const float L = log1pf(e);                       // log(1 + exp(-|x|))
-  const float p1 = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);   // sigmoid(x)
-  const float q1 = x >= 0.f ? e / (1.0f + e) : 1.0f / (1.0f + e);   // 1 - sigmoid(x)
-  const float nlp = L - fminf(x, 0.f);             // -log p
-  const float nlq = L + fmaxf(x, 0.f);             // -log(1-p)
-  const float qg = powg(q1, gamma), pg = powg(p1, gamma);
-  const float wpos = y * alpha * qg;
-  const float wneg = (1.0f - y) * (1.0f - alpha) * pg;
-  *g = -wpos * (gamma * p1 * nlp + q1) + wneg * (gamma * q1 * nlq + p1);
-  return wpos * nlp + wneg * nlq;
-}
+// powg / focal_term (the reference's stable focal form, fcos.py:443-462): fcos_focal.h
 
 // One cell's loss terms and gradients: t(i) targets[i], xc(c) class logit c, xr(j) box / centerness
 // prediction j; putc(c, g) / putcen(g) / putr(j, g) receive the SCALED gradients (class c, the

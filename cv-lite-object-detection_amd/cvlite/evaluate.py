@@ -510,16 +510,17 @@ def _row_scale(extra, real):
 
 def evaluate_fcos(model, samples, num_classes, batch_size=16, protocol="voc07", center=False, iou_thresholds=None,
                   max_dets=100, fold_bn=False, area_ranges=None, shard=None, group=None, return_state=False,
-                  **detect_kwargs):
+                  clamp_reg=False, **detect_kwargs):
     """FCOS (cvlite.fcos.build_model or its FCOSNet): infer_fcos.image_detections per batch, then
     Evaluator.add on its device outputs.  detect_kwargs: iou_thresh, cls_thresh, max_detections,
     max_total_size of image_detections.  fold_bn: the forwards run with the backbone's BatchNorms
-    folded into its convs (folded once, before the first batch).  Returns Evaluator.result()."""
+    folded into its convs (folded once, before the first batch).  clamp_reg: image_detections' clamp of
+    the box outputs at 0 (networks trained with the FCOS papers' recipe).  Returns Evaluator.result()."""
     from .infer_fcos import image_detections
     ev = Evaluator(num_classes, protocol, iou_thresholds=iou_thresholds, max_dets=max_dets, area_ranges=area_ranges)
     for imgs, gt, ids, real, extra in _sample_batches(samples, batch_size, shard, areas=area_ranges is not None):
         det = image_detections(torch.from_numpy(imgs).cuda(), model, num_classes, center=center, fold_bn=fold_bn,
-                               **detect_kwargs)
+                               clamp_reg=clamp_reg, **detect_kwargs)
         valid = det.valid_detections.clone()
         valid[real:] = 0
         gtb, gtl, gtc, gtf = (t.cuda() for t in gt)

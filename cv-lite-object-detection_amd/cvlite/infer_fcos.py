@@ -24,10 +24,15 @@ CombinedNonMaxSuppression = collections.namedtuple(
 
 
 def detect_from_outputs(reg, cls, shapes, num_classes, center=False, iou_thresh=0.5, cls_thresh=0.05,
-                        max_detections=100, max_total_size=100, strides=STRIDES):
+                        max_detections=100, max_total_size=100, strides=STRIDES, clamp_reg=False):
     """Batched device form over the fused FCOS head outputs: reg [B,P,>=5] (t, b, l, r,
-    centerness), cls [B,P,>=C] fp32, level shapes [(h, w)] x 5 (level-major rows)."""
+    centerness), cls [B,P,>=C] fp32, level shapes [(h, w)] x 5 (level-major rows).
+    clamp_reg (cvlite extension): the four box columns are clamped at 0 first, on a copy -- what the
+    loss of the FCOS papers' recipe (ops_targets.fcos_paper_loss) trains the head outputs under."""
     _lib.require_cuda(reg, cls)
+    if clamp_reg:
+        reg = reg.clone()
+        reg[..., :4].clamp_(min=0)
     B, P = int(reg.shape[0]), int(reg.shape[1])
     assert sum(h * w for h, w in shapes) == P, "shapes do not match the rows"
     hw_arr = (ctypes.c_int32 * 10)(*[int(v) for hwl in shapes for v in hwl])
@@ -50,11 +55,12 @@ def detect_from_outputs(reg, cls, shapes, num_classes, center=False, iou_thresh=
 
 
 def image_detections(image, model, num_classes, center=False, iou_thresh=0.5, cls_thresh=0.05,
-                     max_detections=100, max_total_size=100, fold_bn=False):
+                     max_detections=100, max_total_size=100, fold_bn=False, clamp_reg=False):
     """infer_fcos.py:27-62.  model = cvlite.fcos.build_model(...) (or its FCOSNet); image
     [B,H,W,3] / [H,W,3] fp32 (already resized and scaled to [-1, 1]).  fold_bn (cvlite extension): run
     the forward with the backbone's BatchNorms folded into its convs (FPNDetector.fold_bn; ResNet
-    backbones, bf16) -- the same map up to bf16 rounding, without the BN passes."""
+    backbones, bf16) -- the same map up to bf16 rounding, without the BN passes.  clamp_reg: detect_from_outputs'
+    clamp of the box outputs at 0 (networks trained with the FCOS papers' recipe)."""
     net = getattr(model, "net", model)
     x = torch.as_tensor(image, dtype=torch.float32, device="cuda")
     if x.dim() == 3:
@@ -63,4 +69,4 @@ def image_detections(image, model, num_classes, center=False, iou_thresh=0.5, cl
     shapes, _, _ = net.layout(B, H, W)
     reg, cls = net.forward(x.contiguous(), train=False, folded=bool(fold_bn))
     return detect_from_outputs(reg, cls, shapes, num_classes, center, iou_thresh, cls_thresh, max_detections,
-                               max_total_size)
+                               max_total_size, clamp_reg=clamp_reg)

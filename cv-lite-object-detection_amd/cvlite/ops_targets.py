@@ -112,6 +112,87 @@ def fcos_loss(reg_pred, cls_pred, targets, num_classes, reg_type="l1", grad_scal
     return losses, d_reg, d_cls
 
 
+# ---- the FCOS papers' recipe (cvlite extension; include/cvlite.h states the rules) ----------------
+FCOS_PAPER_BOUNDS = (64.0, 128.0, 256.0, 512.0)   # regress ranges on max(l,t,r,b), Tian et al. 2019
+
+
+def fcos_paper_assign(boxes, nbox, img_dim, pad_hw, num_classes, strides=FCOS_STRIDES, bounds=FCOS_PAPER_BOUNDS,
+                      center_radius=1.5, out=None, num_targets=None):
+    """Batched targets of the FCOS papers (cvl_fcos_paper_assign): per-level regress range on
+    max(l,t,r,b), centre sampling (center_radius strides about the box centre; <= 0: the whole box),
+    smallest-area winner, sqrt centerness, one-hot class.  Inputs and the targets layout are
+    fcos_assign's.  Returns targets [B, P, 5+C] f32 and num_targets [B,5] i32 = the number of
+    POSITIVE CELLS per level (fcos_assign counts boxes)."""
+    B, nmax = _boxes_args(boxes, nbox, img_dim)
+    P = sum(h * w for h, w in fcos_level_shapes(pad_hw[0], pad_hw[1], strides))
+    if out is None:
+        out = torch.empty((B, P, 5 + num_classes), device=boxes.device, dtype=torch.float32)
+    if num_targets is None:
+        num_targets = torch.empty((B, 5), device=boxes.device, dtype=torch.int32)
+    assert tuple(out.shape) == (B, P, 5 + num_classes) and out.dtype == torch.float32 and out.is_contiguous()
+    assert tuple(num_targets.shape) == (B, 5) and num_targets.dtype == torch.int32 and num_targets.is_contiguous()
+    st = (_lib.ctypes.c_int32 * 5)(*[int(s) for s in strides])
+    bd = (_lib.ctypes.c_float * 4)(*[float(x) for x in bounds])
+    _lib.call("cvl_fcos_paper_assign", ptr(boxes), ptr(nbox), ptr(img_dim), B, nmax, int(pad_hw[0]),
+              int(pad_hw[1]), int(num_classes), _lib.ctypes.cast(st, _lib.c_void_p),
+              _lib.ctypes.cast(bd, _lib.c_void_p), float(center_radius), ptr(out), ptr(num_targets),
+              _lib.stream())
+    return out, num_targets
+
+
+def fcos_target_norm(targets, num_classes, out=None):
+    """norm [B,2] f32 = (number of positive cells, sum of their centerness targets) per image; a cell
+    is positive when its largest class target is >= 1 (cvl_fcos_target_norm)."""
+    _lib.require_cuda(targets)
+    B, P = int(targets.shape[0]), int(targets.shape[1])
+    assert targets.dtype == torch.float32 and targets.is_contiguous() and int(targets.shape[2]) == 5 + num_classes
+    if out is None:
+        out = torch.empty((B, 2), device=targets.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, 2) and out.dtype == torch.float32 and out.is_contiguous()
+    ws = torch.empty(int(_lib.load().cvl_fcos_target_norm_workspace_size(B, P)), device=targets.device,
+                     dtype=torch.uint8)
+    _lib.call("cvl_fcos_target_norm", ptr(targets), B, P, int(num_classes), ptr(out), ptr(ws), ws.numel(),
+              _lib.stream())
+    return out
+
+
+def fcos_paper_loss(reg_pred, cls_pred, targets, num_classes, norm=None, grad_scale=1.0, with_grad=True,
+                    grad_dtype=torch.float32, d_reg=None, d_cls=None, alpha=0.25, gamma=2.0, losses=None):
+    """Fused loss of the FCOS papers, forward and backward (cvl_fcos_paper_loss): focal / N,
+    centerness-weighted GIoU on max(pred, 0) / sum(centerness), BCE centerness on the positives / N,
+    with (N, sum centerness) = norm [B,2] as fcos_target_norm returns it (None: plain sums).
+    reg_pred [B,P,ld_reg>=5] f32, cls_pred [B,P,ld_cls>=C] f32, targets [B,P,5+C] f32.
+    Returns (losses [B,3] f32 = (cls, reg, cen) per image, d_reg, d_cls)."""
+    _lib.require_cuda(reg_pred, cls_pred, targets)
+    B, P = int(targets.shape[0]), int(targets.shape[1])
+    assert reg_pred.shape[:2] == (B, P) and cls_pred.shape[:2] == (B, P)
+    assert reg_pred.dtype == torch.float32 and cls_pred.dtype == torch.float32 and targets.dtype == torch.float32
+    assert reg_pred.is_contiguous() and cls_pred.is_contiguous() and targets.is_contiguous()
+    assert int(targets.shape[2]) == 5 + num_classes
+    dev = targets.device
+    if norm is not None:
+        _lib.require_cuda(norm)
+        assert tuple(norm.shape) == (B, 2) and norm.dtype == torch.float32 and norm.is_contiguous()
+    if losses is None:
+        losses = torch.empty((B, 3), device=dev, dtype=torch.float32)
+    assert losses.shape == (B, 3) and losses.dtype == torch.float32 and losses.is_contiguous()
+    ws = torch.empty(int(_lib.load().cvl_fcos_loss_workspace_size(B, P)), device=dev, dtype=torch.uint8)
+    if with_grad:
+        if d_reg is None:
+            d_reg = torch.empty((B, P, reg_pred.shape[2]), device=dev, dtype=grad_dtype)
+        if d_cls is None:
+            d_cls = torch.empty((B, P, cls_pred.shape[2]), device=dev, dtype=grad_dtype)
+    for d in (d_reg, d_cls):
+        assert d is None or (d.shape[:2] == (B, P) and d.is_contiguous() and d.dtype in (torch.float32, torch.bfloat16))
+    dt = lambda t: 0 if t is None or t.dtype == torch.float32 else 1  # noqa: E731
+    _lib.call("cvl_fcos_paper_loss", ptr(reg_pred), int(reg_pred.shape[2]), ptr(cls_pred), int(cls_pred.shape[2]),
+              ptr(targets), ptr(norm), B, P, int(num_classes), float(grad_scale), float(alpha), float(gamma),
+              ptr(losses), ptr(d_reg), int(d_reg.shape[2]) if d_reg is not None else 0, dt(d_reg),
+              ptr(d_cls), int(d_cls.shape[2]) if d_cls is not None else 0, dt(d_cls), ptr(ws), ws.numel(),
+              _lib.stream())
+    return losses, d_reg, d_cls
+
+
 def _boxes_args(boxes, nbox, img_dim):
     _lib.require_cuda(boxes, nbox, img_dim)
     assert boxes.dtype == torch.float32 and nbox.dtype == torch.int32 and img_dim.dtype == torch.float32

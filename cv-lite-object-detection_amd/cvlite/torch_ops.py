@@ -16,6 +16,10 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           [B, 3] = (cls, reg, cen); autograd = the
                                                           fused kernel's gradients scaled by the
                                                           upstream per-image, per-term gradients
+  torch.ops.cvlite.fcos_paper_assign(boxes, nbox, img_dim, pad_h, pad_w, C, center_radius),
+  torch.ops.cvlite.fcos_target_norm(targets, C),
+  torch.ops.cvlite.fcos_paper_loss(reg, cls, targets, norm, C)  the FCOS papers' recipe (cvlite
+                                                          extension); the loss has autograd as fcos_loss
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -244,6 +248,73 @@ def _loss_backward(ctx, g):
 
 
 fcos_loss.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+# ---- the FCOS papers' recipe (cvlite extension) ----------------------------------------------------
+@torch.library.custom_op("cvlite::fcos_paper_assign", mutates_args=(), device_types="cuda")
+def fcos_paper_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Tensor, pad_h: int, pad_w: int,
+                      num_classes: int, center_radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Targets of the FCOS papers (regress ranges (64, 128, 256, 512), centre sampling, smallest area)
+    -> (targets [B,P,5+C] fp32 level-major, positive cells per level [B,5] i32)."""
+    return ot.fcos_paper_assign(boxes.contiguous(), nbox.contiguous(), img_dim.contiguous(), (pad_h, pad_w),
+                                num_classes, center_radius=center_radius)
+
+
+@fcos_paper_assign.register_fake
+def _(boxes, nbox, img_dim, pad_h, pad_w, num_classes, center_radius):
+    P = sum(h * w for h, w in ot.fcos_level_shapes(pad_h, pad_w))
+    B = boxes.shape[0]
+    return boxes.new_empty((B, P, 5 + num_classes)), nbox.new_empty((B, 5))
+
+
+@torch.library.custom_op("cvlite::fcos_target_norm", mutates_args=(), device_types="cuda")
+def fcos_target_norm(targets: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """targets [B,P,5+C] -> [B,2] = (number of positive cells, sum of their centerness targets)."""
+    return ot.fcos_target_norm(targets.contiguous(), num_classes)
+
+
+@fcos_target_norm.register_fake
+def _(targets, num_classes):
+    return targets.new_empty((targets.shape[0], 2))
+
+
+@torch.library.custom_op("cvlite::fcos_paper_loss", mutates_args=(), device_types="cuda")
+def fcos_paper_loss(reg: torch.Tensor, cls: torch.Tensor, targets: torch.Tensor, norm: Optional[torch.Tensor],
+                    num_classes: int) -> torch.Tensor:
+    """Loss of the FCOS papers per image: reg [B,P,>=5] fp32, cls [B,P,>=C] fp32, targets [B,P,5+C],
+    norm [B,2] from fcos_target_norm (None: plain sums) -> [B,3] = (cls, reg, cen)."""
+    losses, _, _ = ot.fcos_paper_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), num_classes,
+                                      norm=None if norm is None else norm.contiguous(), with_grad=False)
+    return losses
+
+
+@fcos_paper_loss.register_fake
+def _(reg, cls, targets, norm, num_classes):
+    return reg.new_empty((reg.shape[0], 3))
+
+
+def _paper_loss_setup(ctx, inputs, output):
+    reg, cls, targets, norm, C = inputs
+    ctx.save_for_backward(reg, cls, targets, norm)
+    ctx.C = C
+
+
+def _paper_loss_backward(ctx, g):
+    reg, cls, targets, norm = ctx.saved_tensors
+    _, d_reg, d_cls = ot.fcos_paper_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), ctx.C,
+                                         norm=None if norm is None else norm.contiguous(), grad_scale=1.0)
+    g = g.to(torch.float32)
+    # cls term -> class logits; reg term -> ltrb channels 0..3; centerness term -> channel 4;
+    # padding channels get exactly zero
+    cscale = torch.zeros((reg.shape[0], 1, cls.shape[2]), dtype=torch.float32, device=reg.device)
+    cscale[:, 0, :ctx.C] = g[:, 0:1]
+    rscale = torch.zeros((reg.shape[0], 1, reg.shape[2]), dtype=torch.float32, device=reg.device)
+    rscale[:, 0, :4] = g[:, 1:2]
+    rscale[:, 0, 4] = g[:, 2]
+    return d_reg * rscale, d_cls * cscale, None, None, None
+
+
+fcos_paper_loss.register_autograd(_paper_loss_backward, setup_context=_paper_loss_setup)
 
 
 # ---- optimizer -----------------------------------------------------------------------------------

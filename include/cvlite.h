@@ -109,6 +109,60 @@ int cvl_fcos_center_v1_assign(const float* boxes, const int32_t* nbox, const flo
                               float* targets, int32_t* num_targets, cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The FCOS recipe of the FCOS papers (Tian et al., ICCV 2019 / TPAMI 2020): an extension beyond the
+ * reference, whose own recipe is cvl_fcos_assign / cvl_fcos_loss above.
+ *
+ * cvl_fcos_paper_assign: inputs, layout and channel order of cvl_fcos_assign (targets [B][P][5+C] =
+ * (top, bottom, left, right) in stride units, centerness, C class values; n_max <= 256; the staged
+ * tile limits C to 219) plus center_radius.  num_targets [B][5] is the number of POSITIVE CELLS per
+ * level (cvl_fcos_assign counts boxes).  All fp32, in this operation order (no contraction):
+ *   box i < clamp(nbox[b], 0, n_max) with (int)label in [0, C) (others are skipped entirely):
+ *     yc = r0*H, xc = r1*W, hp = r2*H, wp = r3*W; y0 = yc - hp*0.5f, y1 = yc + hp*0.5f,
+ *     x0 = xc - wp*0.5f, x1 = xc + wp*0.5f; area = hp*wp
+ *   cell (cy, cx) of level l, sf = (float)stride_l: gy = ((float)cy + 0.5f)*sf, gx likewise;
+ *     t = gy - y0, b = y1 - gy, l = gx - x0, r = x1 - gx, m = max(t, b, l, r)
+ *   inside: center_radius <= 0: min(t, b, l, r) > 0; otherwise rs = center_radius*sf,
+ *     sy0 = fmaxf(y0, yc - rs), sy1 = fminf(y1, yc + rs), the same in x, and
+ *     min(gy - sy0, sy1 - gy, gx - sx0, sx1 - gx) > 0
+ *   range: lo_l <= m <= hi_l, lo = (-1, size_bounds[0..3]), hi = (size_bounds[0..3], +inf), both
+ *     ends inclusive (m exactly on a bound is a candidate on both levels)
+ *   winner among the candidates: smallest area, ties to the lowest box index
+ *   values: (t, b, l, r)/sf; centerness = (float)sqrt((min(t,b)/max(t,b)) * (min(l,r)/max(l,r))) with
+ *     the four pixel distances cast to double first; a one-hot class.  Cells without a candidate are
+ *     all zero.
+ *
+ * cvl_fcos_target_norm: norm[b] = (n_pos, sum of targets[4] over the positive cells) of image b, a cell
+ * being positive when max_c targets[5+c] >= 1 (the mask of cvl_fcos_loss); summed in float64 in a
+ * fixed order.  workspace >= cvl_fcos_target_norm_workspace_size(B, P) bytes.
+ *
+ * cvl_fcos_paper_loss: fused forward + backward with the conventions of cvl_fcos_loss (reg_pred
+ * [B][P][ld_reg >= 5], cls_pred [B][P][ld_cls >= C], optional d_reg / d_cls fp32 (0) or bf16 (1) with
+ * padding columns zeroed, grad_scale, losses [B][3] = (cls, reg, cen), workspace >=
+ * cvl_fcos_loss_workspace_size(B, P) bytes).  norm [B][2] as cvl_fcos_target_norm writes it, or null.
+ * Per image, N = max(norm[b][0], 1), Wsum = max(norm[b][1], 1e-6f) (null norm: N = Wsum = 1):
+ *   cls = (1/N) sum_cells sum_c focal(y, x)              (the focal term of cvl_fcos_loss_ex)
+ *   cen = (1/N) sum_pos [max(x,0) - x t4 + log1p(exp(-|x|))], x = reg_pred[4]; d/dx = sigmoid(x) - t4
+ *   reg = (1/Wsum) sum_pos t4 (1 - GIoU)
+ * GIoU on d_j = max(p_j, 0) (gradient 0 where p_j <= 0); th = t0+t1, tw = t2+t3, ph = d0+d1, pw = d2+d3:
+ *   I = (min(t0,d0)+min(t1,d1)) (min(t2,d2)+min(t3,d3)), U = th tw + ph pw - I + 1e-12,
+ *   E = (max(t0,d0)+max(t1,d1)) (max(t2,d2)+max(t3,d3)) + 1e-12, GIoU = I/U - (E - U)/E.
+ * Non-positive cells contribute nothing to cen / reg and get zero box gradients.  Per-image sums are
+ * deterministic (float64 per-tile partials, fixed-order second pass).
+ * ---------------------------------------------------------------------------------------- */
+int cvl_fcos_paper_assign(const float* boxes, const int32_t* nbox, const float* img_dim, int B, int n_max,
+                          int pad_h, int pad_w, int num_classes, const int32_t* strides /*host[5]*/,
+                          const float* size_bounds /*host[4]*/, float center_radius, float* targets,
+                          int32_t* num_targets, cvl_stream_t stream);
+size_t cvl_fcos_target_norm_workspace_size(int B, int P);
+int cvl_fcos_target_norm(const float* targets, int B, int P, int num_classes, float* norm, void* workspace,
+                         size_t workspace_bytes, cvl_stream_t stream);
+int cvl_fcos_paper_loss(const float* reg_pred, int ld_reg, const float* cls_pred, int ld_cls,
+                        const float* targets, const float* norm, int B, int P, int num_classes,
+                        float grad_scale, float alpha, float gamma, float* losses, void* d_reg, int ld_dreg,
+                        int dreg_dtype, void* d_cls, int ld_dcls, int dcls_dtype, void* workspace,
+                        size_t workspace_bytes, cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Segmented implicit-GEMM convolution (bf16 MFMA, fp32 accumulate).  Replaces every Conv2D of
  * the reference graphs (Keras ResNet50 backbone; FCOS/fcos.py:49-101 FPN, towers and heads;
  * RetinaNet/retinanet_module.py:74-148) forward (mode FWD) and backward-input (mode DGRAD).
