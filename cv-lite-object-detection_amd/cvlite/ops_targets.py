@@ -193,6 +193,40 @@ def fcos_paper_loss(reg_pred, cls_pred, targets, num_classes, norm=None, grad_sc
     return losses, d_reg, d_cls
 
 
+def fcos_atss_assign(boxes, nbox, img_dim, pad_hw, num_classes, strides=FCOS_STRIDES, topk=9, anchor_scale=8.0,
+                     out=None, num_targets=None, return_candidates=False):
+    """Batched ATSS targets (cvl_fcos_atss_assign; include/cvlite.h states the rule): per box the topk
+    grid points nearest its centre on every level, positives where the anchor IoU (square anchors of
+    side anchor_scale * stride) reaches mean + std of the box's own candidates and the point lies
+    inside the box; per cell the largest IoU wins.  Inputs, the targets layout and num_targets (positive
+    cells per level) are fcos_paper_assign's, and fcos_target_norm / fcos_paper_loss take the result.
+    The contest workspace comes from torch's caching allocator, as the neighbours' workspaces do.
+    return_candidates: also (cand_cells [B,n_max,5*topk] i32, cand_iou the same shape f32, cand_thr
+    [B,n_max] f64), the selection as the kernel saw it."""
+    B, nmax = _boxes_args(boxes, nbox, img_dim)
+    P = sum(h * w for h, w in fcos_level_shapes(pad_hw[0], pad_hw[1], strides))
+    dev = boxes.device
+    if out is None:
+        out = torch.empty((B, P, 5 + num_classes), device=dev, dtype=torch.float32)
+    if num_targets is None:
+        num_targets = torch.empty((B, 5), device=dev, dtype=torch.int32)
+    assert tuple(out.shape) == (B, P, 5 + num_classes) and out.dtype == torch.float32 and out.is_contiguous()
+    assert tuple(num_targets.shape) == (B, 5) and num_targets.dtype == torch.int32 and num_targets.is_contiguous()
+    cand = (None, None, None)
+    if return_candidates:
+        slots = 5 * max(int(topk), 0)
+        cand = (torch.empty((B, nmax, slots), device=dev, dtype=torch.int32),
+                torch.empty((B, nmax, slots), device=dev, dtype=torch.float32),
+                torch.empty((B, nmax), device=dev, dtype=torch.float64))
+    ws = torch.empty(int(_lib.load().cvl_fcos_atss_workspace_size(B, P)), device=dev, dtype=torch.uint8)
+    st = (_lib.ctypes.c_int32 * 5)(*[int(s) for s in strides])
+    _lib.call("cvl_fcos_atss_assign", ptr(boxes), ptr(nbox), ptr(img_dim), B, nmax, int(pad_hw[0]),
+              int(pad_hw[1]), int(num_classes), _lib.ctypes.cast(st, _lib.c_void_p), int(topk),
+              float(anchor_scale), ptr(out), ptr(num_targets), ptr(cand[0]), ptr(cand[1]), ptr(cand[2]), ptr(ws),
+              ws.numel(), _lib.stream())
+    return (out, num_targets) + cand if return_candidates else (out, num_targets)
+
+
 def _boxes_args(boxes, nbox, img_dim):
     _lib.require_cuda(boxes, nbox, img_dim)
     assert boxes.dtype == torch.float32 and nbox.dtype == torch.int32 and img_dim.dtype == torch.float32

@@ -20,6 +20,9 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
   torch.ops.cvlite.fcos_target_norm(targets, C),
   torch.ops.cvlite.fcos_paper_loss(reg, cls, targets, norm, C)  the FCOS papers' recipe (cvlite
                                                           extension); the loss has autograd as fcos_loss
+  torch.ops.cvlite.fcos_atss_assign(boxes, nbox, img_dim, pad_h, pad_w, C, topk, anchor_scale)
+                                                          ATSS targets (cvlite extension) for the
+                                                          same fcos_target_norm / fcos_paper_loss
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -262,6 +265,23 @@ def fcos_paper_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Te
 
 @fcos_paper_assign.register_fake
 def _(boxes, nbox, img_dim, pad_h, pad_w, num_classes, center_radius):
+    P = sum(h * w for h, w in ot.fcos_level_shapes(pad_h, pad_w))
+    B = boxes.shape[0]
+    return boxes.new_empty((B, P, 5 + num_classes)), nbox.new_empty((B, 5))
+
+
+@torch.library.custom_op("cvlite::fcos_atss_assign", mutates_args=(), device_types="cuda")
+def fcos_atss_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Tensor, pad_h: int, pad_w: int,
+                     num_classes: int, topk: int, anchor_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ATSS targets (the topk nearest grid points per level, IoU threshold mean + std per box, largest
+    IoU per cell) -> (targets [B,P,5+C] fp32 level-major, positive cells per level [B,5] i32); the
+    loss op is fcos_paper_loss."""
+    return ot.fcos_atss_assign(boxes.contiguous(), nbox.contiguous(), img_dim.contiguous(), (pad_h, pad_w),
+                               num_classes, topk=topk, anchor_scale=anchor_scale)
+
+
+@fcos_atss_assign.register_fake
+def _(boxes, nbox, img_dim, pad_h, pad_w, num_classes, topk, anchor_scale):
     P = sum(h * w for h, w in ot.fcos_level_shapes(pad_h, pad_w))
     B = boxes.shape[0]
     return boxes.new_empty((B, P, 5 + num_classes)), nbox.new_empty((B, 5))

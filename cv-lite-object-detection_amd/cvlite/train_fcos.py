@@ -39,7 +39,7 @@ class FCOSTrainer(GraphStepper):
     def __init__(self, net, batch_size, image_hw, n_max=16, init_lr=5e-4, min_lr=1e-5, decay_step=1000,
                  decay_rate=0.9, momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0,
                  world=1, use_graph=True, st_step=0, targets="fcos", center_only=True, optimizer=None,
-                 max_decays=None, center_radius=1.5, bounds=None):
+                 max_decays=None, center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0):
         self.net = net
         # optimizer: None or SGD -> Keras SGD with `momentum` (train_fcos.py:284-285); an Adam
         # (cvlite.train_centernet.Adam, the tf.optimizers.Adam() stand-in) -> Keras Adam, what the
@@ -69,11 +69,15 @@ class FCOSTrainer(GraphStepper):
         # "paper" (cvlite extension): the recipe of the FCOS papers -- fcos_paper_assign (centre sampling
         # with center_radius, regress ranges `bounds`, None = FCOS_PAPER_BOUNDS), fcos_target_norm and
         # fcos_paper_loss (GIoU, BCE centerness, per-image normalisation by the positives)
-        if targets not in ("fcos", "center", "center_v1", "paper"):
-            raise ValueError("targets must be 'fcos', 'center', 'center_v1' or 'paper'")
-        if targets == "paper" and hasattr(net, "cen_heads"):
-            raise ValueError("targets='paper' needs the FCOS network, not a centre variant")
+        # "atss" (cvlite extension): fcos_atss_assign (the atss_topk nearest grid points per level, anchors
+        # of side atss_scale * stride, IoU threshold mean + std per box) in front of the same
+        # fcos_target_norm and fcos_paper_loss
+        if targets not in ("fcos", "center", "center_v1", "paper", "atss"):
+            raise ValueError("targets must be 'fcos', 'center', 'center_v1', 'paper' or 'atss'")
+        if targets in ("paper", "atss") and hasattr(net, "cen_heads"):
+            raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
         self.target_kind, self.center_only = targets, center_only
+        self.atss_topk, self.atss_scale = int(atss_topk), float(atss_scale)
         self.center_radius = float(center_radius)
         self.bounds = tuple(float(v) for v in (ot.FCOS_PAPER_BOUNDS if bounds is None else bounds))
         # the centre networks (cvlite.fcos_center_net): focal centerness from the cls-tower head in
@@ -96,7 +100,7 @@ class FCOSTrainer(GraphStepper):
         self.d_reg = torch.zeros((B, self.P, 32), dtype=act, device=dev)
         self.d_cls = torch.zeros((B, self.P, net.cls_ld), dtype=act, device=dev)
         self.losses = torch.zeros((B, 3), dtype=torch.float32, device=dev)
-        self.norm = torch.zeros((B, 2), dtype=torch.float32, device=dev) if targets == "paper" else None
+        self.norm = torch.zeros((B, 2), dtype=torch.float32, device=dev) if targets in ("paper", "atss") else None
         # the heads' fp32 outputs, zeroed once (FCOSNet writes only the used columns; see
         # FCOSNet._heads_forward) -- lent to the network for the step's forward only
         self._head_out = ((torch.zeros((B, self.P, net.reg_ld), dtype=torch.float32, device=dev),
@@ -120,6 +124,11 @@ class FCOSTrainer(GraphStepper):
                                          bounds=self.bounds, center_radius=self.center_radius, out=self.targets,
                                          num_targets=self.ntgt)
             ot.fcos_target_norm(tg, self.C, out=self.norm)
+        elif self.target_kind == "atss":
+            tg, _ = ot.fcos_atss_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
+                                        topk=self.atss_topk, anchor_scale=self.atss_scale, out=self.targets,
+                                        num_targets=self.ntgt)
+            ot.fcos_target_norm(tg, self.C, out=self.norm)
         elif self.target_kind == "center":
             tg, _ = ot.fcos_center_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
                                           center_only=self.center_only, out=self.targets, num_targets=self.ntgt)
@@ -135,7 +144,7 @@ class FCOSTrainer(GraphStepper):
         finally:
             self.net.head_out = None
         self.outputs = (reg, cls)                 # head outputs of the last step (graph memory)
-        if self.target_kind == "paper":
+        if self.target_kind in ("paper", "atss"):
             ot.fcos_paper_loss(reg, cls, tg, self.C, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
                                d_cls=self.d_cls, losses=self.losses)
         else:
@@ -188,7 +197,7 @@ class JitterFCOSTrainer(object):
     def __init__(self, net, batch_size, n_max=16, init_lr=5e-4, min_lr=1e-5, decay_step=1000, decay_rate=0.9,
                  momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0, st_step=0, use_graph=True,
                  max_buckets=12, world=1, optimizer=None, max_decays=None, targets="fcos", center_radius=1.5,
-                 bounds=None):
+                 bounds=None, atss_topk=9, atss_scale=8.0):
         # world > 1: data-parallel (dist.py) -- each rank runs its own bs images through its buckets,
         # the summed gradient is all-reduced (one bucketed SUM over RCCL) before the shared update
         # with 1 / (world * bs); the buckets differ per rank, so there is no overlap with the backward
@@ -198,11 +207,12 @@ class JitterFCOSTrainer(object):
         self.max_decays = max_decays
         self.sched = (init_lr, min_lr, decay_rate, decay_step)
         self.reg_type, self.use_graph, self.max_buckets = reg_type, use_graph, max_buckets
-        # targets / center_radius / bounds: forwarded to every bucket's FCOSTrainer ("paper": the FCOS
-        # papers' recipe)
-        if targets == "paper" and hasattr(net, "cen_heads"):
-            raise ValueError("targets='paper' needs the FCOS network, not a centre variant")
-        self.bucket_kw = dict(targets=targets, center_radius=center_radius, bounds=bounds)
+        # targets / center_radius / bounds / atss_topk / atss_scale: forwarded to every bucket's FCOSTrainer
+        # ("paper": the FCOS papers' recipe; "atss": ATSS targets under the same loss)
+        if targets in ("paper", "atss") and hasattr(net, "cen_heads"):
+            raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
+        self.bucket_kw = dict(targets=targets, center_radius=center_radius, bounds=bounds, atss_topk=atss_topk,
+                              atss_scale=atss_scale)
         self.weight_decay = float(weight_decay)
         self.l2 = nn.L2Reg(net.store) if self.weight_decay > 0.0 else None
         dev = net.device
@@ -367,7 +377,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
           init_lr=1.0e-3, min_lr=1.0e-5, decay_step=1000, decay_rate=0.99, display_step=50, step_save=100,
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
           max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07",
-          eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None):
+          eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -403,7 +413,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       GIoU, BCE centerness, losses normalised per image by the positives inside the loss -- the
       gradient divisor stays 1 / (batch_size * world)), and "Average Objs" then counts positive cells;
       the eval_data hook evaluates with the box outputs clamped at 0 (clamp_reg=True), as that loss
-      trains them.
+      trains them.  "atss" = ATSS targets (FCOSTrainer(targets="atss", atss_topk, atss_scale)) under the
+      same loss, divisor, "Average Objs" and clamped evaluation.
     The reference's thermal "Cooling GPU" sleep runs only with CVL_COOLING=1.  Returns None."""
     from . import checkpoint as ck
     import torch.distributed as tdist
@@ -421,9 +432,15 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
         raise ValueError("train_data holds %d samples, fewer than world * batch_size" % n_data)
     say = print if rank == 0 else (lambda *a, **k: None)
     momentum = float(getattr(optimizer, "momentum", 0.9))
-    if recipe not in ("reference", "paper"):
-        raise ValueError("recipe must be 'reference' or 'paper', not %r" % (recipe,))
-    recipe_kw = dict(targets="paper", center_radius=center_radius, bounds=bounds) if recipe == "paper" else {}
+    if recipe not in ("reference", "paper", "atss"):
+        raise ValueError("recipe must be 'reference', 'paper' or 'atss', not %r" % (recipe,))
+    if recipe == "atss" and hasattr(net, "cen_heads"):
+        raise ValueError("recipe='atss' needs the FCOS network, not a centre variant")
+    recipe_kw = {}
+    if recipe == "paper":
+        recipe_kw = dict(targets="paper", center_radius=center_radius, bounds=bounds)
+    elif recipe == "atss":
+        recipe_kw = dict(targets="atss", atss_topk=atss_topk, atss_scale=atss_scale)
     if raw:          # reference-format samples: per-image jittered sizes, shape-bucketed step
         n_max = max(16, max(len(s["objects"]["label"]) for s in train_data))
         trainer = JitterFCOSTrainer(net, batch_size, n_max=n_max, init_lr=init_lr, min_lr=min_lr,
@@ -514,7 +531,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
         if eval_data is not None and eval_every > 0 and (step + 1) % eval_every == 0 and rank == 0:
             from .evaluate import evaluate_fcos
             res = evaluate_fcos(net, eval_data, net.C, batch_size=batch_size, protocol=eval_protocol,
-                                fold_bn=eval_fold_bn, clamp_reg=recipe == "paper")
+                                fold_bn=eval_fold_bn, clamp_reg=recipe in ("paper", "atss"))
             say("Eval mAP:", str(res["mAP"]))
         if (step + 1) % step_cool == 0:
             say("Trend Loss:", str(round(trend_loss / step_cool, 5)))

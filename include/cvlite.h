@@ -163,6 +163,50 @@ int cvl_fcos_paper_loss(const float* reg_pred, int ld_reg, const float* cls_pred
                         size_t workspace_bytes, cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ATSS target assignment for FCOS (Zhang et al., CVPR 2020, "Bridging the Gap Between Anchor-based and
+ * Anchor-free Detection via Adaptive Training Sample Selection"): an extension beyond the reference.
+ * Its targets feed cvl_fcos_target_norm and cvl_fcos_paper_loss above, the loss ATSS trains FCOS with.
+ *
+ * cvl_fcos_atss_assign: inputs, target layout and channel order of cvl_fcos_paper_assign (boxes
+ * [B][n_max][5] = (yc, xc, h, w, label) normalised, nbox [B], img_dim [B][2], strides HOST [5]; targets
+ * [B][P][5+C] level-major over the (pad_h/stride) x (pad_w/stride) maps; num_targets [B][5] = POSITIVE
+ * CELLS per level; n_max <= 256; the staged tile limits C to 219).  topk in 1..16 (the papers' 9),
+ * anchor_scale > 0 (the papers' 8); anything outside these limits returns the invalid-argument status
+ * and writes nothing.  fp32 in this operation order (no contraction) except where float64 is named:
+ *   box i < clamp(nbox[b], 0, n_max): yc, xc, hp, wp, y0, y1, x0, x1, area as in cvl_fcos_paper_assign;
+ *     the box is skipped entirely unless (int)label is in [0, C) (tested as -1 < label < C, so a NaN
+ *     label is skipped) and area > 0 (which drops a NaN size)
+ *   1 candidates, per level l with Hs x Ws cells, sf = (float)stride_l: gy = ((float)cy + 0.5f)*sf, gx
+ *     likewise; dy = gy - yc, dx = gx - xc, d2 = dy*dy + dx*dx; the candidates are the
+ *     k_l = min(topk, Hs*Ws) cells with the smallest d2, ties to the lowest row-major cell index,
+ *     ranked in that order (d2 orders by its bit pattern, a NaN above +inf)
+ *   2 anchor IoU of a candidate: ha = anchor_scale*sf*0.5f;
+ *     ih = fmaxf(fminf(y1, gy+ha) - fmaxf(y0, gy-ha), 0), iw likewise in x; inter = ih*iw;
+ *     uni = ((ha+ha)*(ha+ha) + area) - inter; iou = (float)((double)inter / (double)uni)
+ *   3 threshold, float64, over the n = sum_l k_l candidates level-major and then by rank:
+ *     mean = (sum iou)/n; var = sum (iou-mean)^2 / (n-1); std = sqrt(var) (the sample standard
+ *     deviation, as the published implementations; 0 for n < 2); thr = mean + std
+ *   4 positive pair (box, cell): the cell is a candidate of the box, (double)iou >= thr, and each of
+ *     t = gy - y0, b = y1 - gy, l = gx - x0, r = x1 - gx is > 0.01f (so min(t, b, l, r) > 0.01f, and a
+ *     NaN distance is never positive).  A pair with iou == 0 that passes both is still positive.
+ *   per cell: among its positive pairs the largest iou wins, ties to the lowest box index; values as
+ *     cvl_fcos_paper_assign: (t, b, l, r)/sf, centerness = (float)sqrt((min(t,b)/max(t,b)) *
+ *     (min(l,r)/max(l,r))) in float64, a one-hot class.  Cells without a positive pair are all zero.
+ * Optional outputs (null: not written), how the tests see inside the assignment: cand_cells int32
+ * [B][n_max][5*topk] = the global cell index in [0, P) by level and rank, or -1; cand_iou float, the same
+ * shape, 0 where cand_cells is -1; cand_thr double [B][n_max]; boxes that are skipped or past nbox get
+ * -1 / 0 / 0.  workspace >= cvl_fcos_atss_workspace_size(B, P) bytes, 8-byte aligned (one 64-bit contest
+ * key per cell).  Graph-safe: no host synchronisation, no allocation; its clears are memset nodes.
+ * Bit-identical from run to run (the contest is an integer max, the counts integer adds).
+ * ---------------------------------------------------------------------------------------- */
+size_t cvl_fcos_atss_workspace_size(int B, int P);
+int cvl_fcos_atss_assign(const float* boxes, const int32_t* nbox, const float* img_dim, int B, int n_max,
+                         int pad_h, int pad_w, int num_classes, const int32_t* strides /*host[5]*/, int topk,
+                         float anchor_scale, float* targets, int32_t* num_targets, int32_t* cand_cells,
+                         float* cand_iou, double* cand_thr, void* workspace, size_t workspace_bytes,
+                         cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Segmented implicit-GEMM convolution (bf16 MFMA, fp32 accumulate).  Replaces every Conv2D of
  * the reference graphs (Keras ResNet50 backbone; FCOS/fcos.py:49-101 FPN, towers and heads;
  * RetinaNet/retinanet_module.py:74-148) forward (mode FWD) and backward-input (mode DGRAD).
