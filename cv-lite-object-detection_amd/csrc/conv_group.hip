@@ -330,15 +330,19 @@ bool gc_ok(int B, int H, int W, int C, int Cg, int stride, int Ho, int Wo) {
 
 // y tiles per workgroup: walk up to 4 tiles on one set of weight registers while that leaves the
 // machine a few workgroups per CU
+// (CVL_DISPATCH=gc_tpw=1|2|4: a test hook -- the walk at small sizes; a value above tiles_y is legal,
+// the walk clamps at the column's last tile)
 inline int gc_tpw(long wgs_at_1, int tiles_y) {
+  const int forced = cvl_dispatch_int("gc_tpw", 0);
+  if (forced == 1 || forced == 2 || forced == 4) return forced;
   int tpw = 1;
   while (tpw < 4 && tpw * 2 <= tiles_y && wgs_at_1 / (tpw * 2) >= 1024) tpw *= 2;
   return tpw;
 }
 
+// the tiling of one launch (the one place it is decided: gc_launch and cvl_gconv3x3_plan)
 template <int MODE, int S>
-int gc_launch(const void* src, const void* wp, void* dst, acc_u64* stats, int B, int Hs, int Ws, int Hd, int Wd, int C,
-              float beta, hipStream_t s) {
+GcGeo gc_geo(int B, int Hs, int Ws, int Hd, int Wd, int C) {
   using T = GcTile<MODE, S>;
   GcGeo g;
   g.B = B; g.Hs = Hs; g.Ws = Ws; g.Hd = Hd; g.Wd = Wd; g.C = C; g.nslab = C / 32;
@@ -346,6 +350,15 @@ int gc_launch(const void* src, const void* wp, void* dst, acc_u64* stats, int B,
   g.tiles_y = (Hd + T::TH - 1) / T::TH;
   g.tpw = gc_tpw((long)g.tiles_x * g.tiles_y * B * g.nslab, g.tiles_y);
   g.ychunks = (g.tiles_y + g.tpw - 1) / g.tpw;
+  g.beta = 0.f;
+  g.slots = 0;
+  return g;
+}
+
+template <int MODE, int S>
+int gc_launch(const void* src, const void* wp, void* dst, acc_u64* stats, int B, int Hs, int Ws, int Hd, int Wd, int C,
+              float beta, hipStream_t s) {
+  GcGeo g = gc_geo<MODE, S>(B, Hs, Ws, Hd, Wd, C);
   g.beta = beta;
   g.slots = cvl_bn_acc_slots();
   const long wgs = (long)g.tiles_x * g.ychunks * B * g.nslab;
@@ -368,7 +381,10 @@ GwPlan gw_plan(int B, int H, int W, int C, int Cg, int stride, int Ho, int Wo) {
   g.tiles_x = (Wo + 15) / 16;
   g.tiles_y = (Ho + th - 1) / th;
   g.ntiles = (long)B * g.tiles_x * g.tiles_y;
-  long want = 1024 / g.nslab;                          // ~1024 workgroups
+  // ~1024 workgroups (CVL_DISPATCH=gw_wgs=N, N >= 1: a test hook -- long chunks on a small map)
+  int target = cvl_dispatch_int("gw_wgs", 1024);
+  if (target < 1) target = 1024;
+  long want = target / g.nslab;
   if (want < 1) want = 1;
   long tpc = (g.ntiles + want - 1) / want;
   if (tpc < 1) tpc = 1;
@@ -406,6 +422,27 @@ extern "C" int cvl_gconv3x3_dgrad(const void* dy, const void* w_dgrad, void* dx,
   CVL_CHECK_ARG(dy && w_dgrad && dx && gc_ok(B, H, W, C, Cg, stride, Ho, Wo));
   if (stride == 1) return gc_launch<0, 1>(dy, w_dgrad, dx, nullptr, B, Ho, Wo, H, W, C, beta, S_);
   return gc_launch<1, 2>(dy, w_dgrad, dx, nullptr, B, Ho, Wo, H, W, C, beta, S_);
+}
+
+extern "C" int cvl_gconv3x3_plan(int kind, int B, int H, int W, int C, int Cg, int stride, int* tpw, int* ychunks,
+                                 int* tiles_x, int* tiles_y, int* tpc, int* nchunk) {
+  CVL_CHECK_ARG(kind >= 0 && kind <= 2 && (stride == 1 || stride == 2));
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  CVL_CHECK_ARG(gc_ok(B, H, W, C, Cg, stride, Ho, Wo));
+  int v[6] = {0, 0, 0, 0, 0, 0};                       // tpw, ychunks, tiles_x, tiles_y, tpc, nchunk
+  if (kind == 2) {
+    const GwPlan p = gw_plan(B, H, W, C, Cg, stride, Ho, Wo);
+    v[2] = p.g.tiles_x; v[3] = p.g.tiles_y; v[4] = p.g.tpc; v[5] = p.nchunk;
+  } else {
+    GcGeo g;
+    if (kind == 0) g = stride == 1 ? gc_geo<0, 1>(B, H, W, Ho, Wo, C) : gc_geo<0, 2>(B, H, W, Ho, Wo, C);
+    else g = stride == 1 ? gc_geo<0, 1>(B, Ho, Wo, H, W, C) : gc_geo<1, 2>(B, Ho, Wo, H, W, C);
+    v[0] = g.tpw; v[1] = g.ychunks; v[2] = g.tiles_x; v[3] = g.tiles_y;
+  }
+  int* out[6] = {tpw, ychunks, tiles_x, tiles_y, tpc, nchunk};
+  for (int i = 0; i < 6; ++i)
+    if (out[i]) *out[i] = v[i];
+  return CVL_OK;
 }
 
 extern "C" size_t cvl_gconv3x3_wgrad_workspace_size(int B, int H, int W, int C, int Cg, int stride) {

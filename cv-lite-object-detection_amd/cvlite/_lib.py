@@ -172,6 +172,7 @@ SIGNATURES = {
     "cvl_gconv3x3_wgrad_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cvl_gconv3x3_wgrad": (c_int, [P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P,
                                    c_size_t, P]),
+    "cvl_gconv3x3_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     "cvl_bn_data_stats_workspace_size": (c_size_t, [c_int]),
     "cvl_bn_data_stats": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, c_size_t, P]),
     "cvl_bn_data_apply": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
@@ -260,7 +261,7 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
          "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan", "cvl_conv_igemm_res_relu",
          "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_", "cvl_eval_match_areas",
-         "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign"}
+         "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign", "cvl_gconv3x3_plan"}
 
 
 def load():

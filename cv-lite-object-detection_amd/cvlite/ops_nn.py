@@ -555,6 +555,19 @@ def gconv3x3_wgrad(x, dy, dw, stride, beta=0.0):
               ptr(ws), ws.numel(), stream())
 
 
+GCONV_KINDS = {"fwd": 0, "dgrad": 1, "wgrad": 2}
+
+
+def gconv3x3_plan(kind, B, H, W, C, Cg, stride):
+    """What the next cvl_gconv3x3_{fwd,dgrad,wgrad} launch on x [B,H,W,C] would use under the current
+    CVL_DISPATCH (cvl_gconv3x3_plan; host only): a dict of tpw, ychunks, tiles_x, tiles_y, tpc, nchunk
+    (0 where the field does not apply).  Raises CvlError for a geometry the kernels reject."""
+    v = [ctypes.c_int(-1) for _ in range(6)]
+    _lib.call("cvl_gconv3x3_plan", GCONV_KINDS[kind], int(B), int(H), int(W), int(C), int(Cg), int(stride),
+              *[ctypes.byref(i) for i in v])
+    return dict(zip(("tpw", "ychunks", "tiles_x", "tiles_y", "tpc", "nchunk"), (int(i.value) for i in v)))
+
+
 def bn_data_stats(img, mean_rstd, run_mean, run_var, eps, momentum):
     """Per-image (mean, rstd) [B,3,2] of the fp32 image [B,H,W,3] + the moving-average update."""
     B, H, W, C = img.shape

@@ -853,6 +853,14 @@ int cvl_gconv3x3_dgrad(const void* dy, const void* w_dgrad, void* dx, int B, int
 size_t cvl_gconv3x3_wgrad_workspace_size(int B, int H, int W, int C, int Cg, int stride);
 int cvl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, float beta, int B, int H, int W, int C, int Cg,
                        int stride, int Ho, int Wo, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
+/* What the next launch with these arguments would use, CVL_DISPATCH hooks (gc_tpw, gw_wgs) included;
+ * host only, touches no device.  kind 0 = fwd, 1 = dgrad, 2 = wgrad.  fwd / dgrad: tpw (destination
+ * tiles a workgroup walks down a column), ychunks = ceil(tiles_y / tpw), the destination tile grid;
+ * wgrad: the output tile grid, tpc (pixel tiles a workgroup accumulates) and nchunk (partials the
+ * reduce sums; workspace = nchunk * 9 * Cg * C * 4 bytes).  Fields that do not apply are written
+ * as 0; any pointer may be null.  CVL_EINVAL for the geometries the kernels reject. */
+int cvl_gconv3x3_plan(int kind, int B, int H, int W, int C, int Cg, int stride, int* tpw, int* ychunks, int* tiles_x,
+                      int* tiles_y, int* tpc, int* nchunk);
 
 /* bn_data: the BatchNormalization(scale=False) on the fp32 input image [B][H][W][3] in front of the
  * ResNeXt stem (retinanet_module.py:53-66).  *_stats: per-image (mean, rstd) [B][3][2] and the

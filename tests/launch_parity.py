@@ -14,7 +14,10 @@ snapshot and compares:
 * BatchNorm finalize / apply / backward (all mask sources), the stem pool forms, max-pool,
   nearest / bilinear up-sampling, ReLU backward, adds, bias gradients, the clip + SGD / Adam
   updates, the weight re-pack, the FCOS / RetinaNet / CenterNet fused losses (float64 autograd of
-  oracle/fcos_torch.py) -- float64 restatements of the kernels' documented semantics.
+  oracle/fcos_torch.py) -- float64 restatements of the kernels' documented semantics;
+* the grouped 3x3 conv of the ResNeXt bottleneck (pack, forward with BN statistics, data gradient,
+  weight gradient): the float64 reference and the per-element bounds of tests/gconv_ref.py, weights
+  decoded from the packed slab image the kernel read (recorded as error / bound, tolerance 1).
 
 Tolerances: bf16 outputs rel-L2 <= 1e-2, fp32 outputs rel-L2 <= 1e-4; every
 conv destination also by its worst row under the same bound (`dst_row`, row_err: a single wrong
@@ -41,6 +44,7 @@ TOL_BF16, TOL_F32 = 1e-2, 1e-4
 NON_COMPUTE = {
     "cvl_wgrad_defer", "cvl_wgrad_flush", "cvl_probe_arm",
     "cvl_bn_acc_decode",          # the harness's own reads of BN accumulator buffers
+    "cvl_gconv3x3_plan",          # host-only plan query (the weight gradient's bound needs nchunk)
 }
 CK_NAMES = {0: "none", 1: "BASE", 2: "BASE_SPLITK", 3: "L64", 4: "L128", 5: "L256", 6: "X256", 7: "X32",
             8: "WG_S", 9: "WG_L128", 10: "WG_L256", 11: "WG_X", 12: "X32H", 13: "WG_SN", 14: "H64", 15: "WG_H",
@@ -1147,6 +1151,94 @@ def check_depthwise_wgrad(lp, name, launch, x, dy, dw, k, stride, pad_t, pad_l, 
     lp.add(name, "dw%d/%d wgrad %dx%dx%d B%d" % (k, stride, H, W, C, B), "dW", red_err(dw.reshape(-1), r, ra), TOL_F32)
 
 
+# ---- grouped 3x3 (the ResNeXt bottleneck): per element, under the derived bounds of gconv_ref.py -------
+def gconv_pack_ref(w, Cg):
+    """cvl_gconv3x3_pack restated: fp32 master [3][3][Cg][C] -> (forward, data-gradient) bf16 slab images
+    [C/32][9][out 32][in 32], zero off the group blocks:
+    Pf[slab][tap][o][i] = w[tap][i % Cg][32 slab + o],  Pd[slab][tap][i][o] = w[8 - tap][i % Cg][32 slab + o]."""
+    C = w.shape[3]
+    ns = C // 32
+    wb = w.to(torch.bfloat16).reshape(9, Cg, ns, 32)                       # [tap][i % Cg][slab][o]
+    ch = torch.arange(32, device=w.device)
+    same = (ch[:, None] // Cg) == (ch[None, :] // Cg)                      # [o][i] (symmetric)
+    full = wb[:, ch % Cg]                                                  # [tap][i][slab][o]
+    pf = torch.where(same, full.permute(2, 0, 3, 1), torch.zeros((), dtype=wb.dtype, device=w.device))
+    pd = torch.where(same, full.flip(0).permute(2, 0, 1, 3), torch.zeros((), dtype=wb.dtype, device=w.device))
+    return pf.contiguous().reshape(-1), pd.contiguous().reshape(-1)
+
+
+def gconv_w_from_fwd(wf, C, Cg):
+    """The master-shaped kernel [3][3][Cg][C] (bf16 values, fp32) a packed forward image holds."""
+    p = wf.view(C // 32, 9, 32, 32).float()                                # [slab][tap][o][i]
+    o = torch.arange(32, device=wf.device)
+    i = (o[None, :] // Cg) * Cg + torch.arange(Cg, device=wf.device)[:, None]          # [ii][o] -> in-slab input
+    return p[:, :, o[None, :], i].permute(1, 2, 0, 3).reshape(3, 3, Cg, C)
+
+
+def gconv_w_from_dgrad(wd, C, Cg):
+    p = wd.view(C // 32, 9, 32, 32).float().flip(1)                        # [slab][tap][i][o]
+    o = torch.arange(32, device=wd.device)
+    i = (o[None, :] // Cg) * Cg + torch.arange(Cg, device=wd.device)[:, None]
+    return p[:, :, i, o[None, :]].permute(1, 2, 0, 3).reshape(3, 3, Cg, C)
+
+
+def _gconv_ratio(lp, name, detail, what, got, t, bound):
+    import gconv_ref
+    lp.add(name, detail, what, gconv_ref.ratio((got.double() - t).abs(), bound), 1.0, "GCONV")
+
+
+def _gconv_detail(kind, B, H, W, C, Cg, s):
+    return "g3x3 %s /%d %dx%dx%d Cg%d B%d" % (kind, s, H, W, C, Cg, B)
+
+
+def check_gconv_pack(lp, name, launch, w, w_fwd=None, w_dgrad=None):
+    launch(w, w_fwd, w_dgrad)
+    Cg, C = int(w.shape[2]), int(w.shape[3])
+    pf, pd = gconv_pack_ref(w, Cg)
+    if w_fwd is not None:
+        lp.exact(name, "g3x3 pack C%d Cg%d" % (C, Cg), "w_fwd", w_fwd, pf, "GCONV")
+    if w_dgrad is not None:
+        lp.exact(name, "g3x3 pack C%d Cg%d" % (C, Cg), "w_dgrad", w_dgrad, pd, "GCONV")
+
+
+def check_gconv_fwd(lp, name, launch, x, w_fwd, y, Cg, stride, stats=None):
+    import gconv_ref
+    st0 = stats.clone() if stats is not None else None
+    launch(x, w_fwd, y, Cg, stride, stats)
+    B, H, W, C = x.shape
+    imgs = lp.img_set(B)
+    d = _gconv_detail("fwd", B, H, W, C, Cg, stride)
+    t, A = gconv_ref.fwd_ref(x[imgs], gconv_w_from_fwd(w_fwd, C, Cg), Cg, stride)
+    _gconv_ratio(lp, name, d, "y", y[imgs], t, gconv_ref.out_bound(t, A))
+    if stats is not None:
+        got = _acc(stats, B, C) - _acc(st0, B, C)
+        S, bound = gconv_ref.stats_ref(y)
+        _gconv_ratio(lp, name, d, "bn_stats", got, S, bound)
+
+
+def check_gconv_dgrad(lp, name, launch, dy, w_dgrad, dx, Cg, stride, beta=0.0):
+    import gconv_ref
+    old = dx.clone() if beta else None
+    launch(dy, w_dgrad, dx, Cg, stride, beta=beta)
+    B, H, W, C = dx.shape
+    imgs = lp.img_set(B)
+    t, A = gconv_ref.dgrad_ref(dy[imgs], gconv_w_from_dgrad(w_dgrad, C, Cg), Cg, stride, H, W, beta=float(beta),
+                               old=old[imgs] if beta else None)
+    _gconv_ratio(lp, name, _gconv_detail("dgrad", B, H, W, C, Cg, stride), "dx", dx[imgs], t, gconv_ref.out_bound(t, A))
+
+
+def check_gconv_wgrad(lp, name, launch, x, dy, dw, stride, beta=0.0):
+    import gconv_ref
+    old = dw.clone() if beta else None
+    launch(x, dy, dw, stride, beta=beta)
+    B, H, W, C = x.shape
+    Cg = int(dw.shape[2])
+    nchunk = lp.nn.gconv3x3_plan("wgrad", B, H, W, C, Cg, stride)["nchunk"]
+    t, A = gconv_ref.wgrad_ref(x, dy, Cg, stride, beta=float(beta), old=old)
+    _gconv_ratio(lp, name, _gconv_detail("wgrad", B, H, W, C, Cg, stride), "dW", dw, t,
+                 gconv_ref.dw_bound(A, B * dy.shape[1] * dy.shape[2], nchunk))
+
+
 def check_maxpool2x2(lp, name, launch, x, y, argmax):
     launch(x, y, argmax)
     B, H, W, C = x.shape
@@ -1315,6 +1407,10 @@ CHECKS = {
     "depthwise_fwd": check_depthwise_fwd,
     "depthwise_dgrad": check_depthwise_dgrad,
     "depthwise_wgrad": check_depthwise_wgrad,
+    "gconv3x3_pack": check_gconv_pack,
+    "gconv3x3_fwd": check_gconv_fwd,
+    "gconv3x3_dgrad": check_gconv_dgrad,
+    "gconv3x3_wgrad": check_gconv_wgrad,
     "maxpool2x2": check_maxpool2x2,
     "maxpool2x2_backward": check_maxpool2x2_backward,
     "upsample_bilinear2x_add": check_upsample_bilinear2x_add,

@@ -68,6 +68,71 @@ def test_pool_and_upsample_restatements():
     torch.testing.assert_close(up, ref)
 
 
+def test_gconv_pack_restatement_and_decode():
+    """The grouped 3x3 slab images: the restated pack written out element by element, and the master
+    kernel the checks decode back from either image."""
+    g = torch.Generator().manual_seed(4)
+    for C, Cg in ((64, 4), (32, 32), (64, 16)):
+        w = torch.randn((3, 3, Cg, C), generator=g)
+        pf, pd = lp.gconv_pack_ref(w, Cg)
+        pf4, pd4 = pf.view(C // 32, 9, 32, 32), pd.view(C // 32, 9, 32, 32)
+        wb = w.to(torch.bfloat16).reshape(9, Cg, C)
+        for slab, tap, a, b in [(0, 0, 0, 0), (C // 32 - 1, 5, 9, 10), (0, 8, 31, 28), (0, 3, 4, 3), (0, 2, 17, 30)]:
+            same = a // Cg == b // Cg
+            # forward [out a][in b]; data gradient [out = input channel a][in = output channel b], tap flipped
+            assert float(pf4[slab, tap, a, b]) == (float(wb[tap, b % Cg, slab * 32 + a]) if same else 0.0)
+            assert float(pd4[slab, tap, a, b]) == (float(wb[8 - tap, a % Cg, slab * 32 + b]) if same else 0.0)
+        assert int((pf4 != 0).sum()) <= 9 * C * Cg
+        want = w.to(torch.bfloat16).float()
+        assert torch.equal(lp.gconv_w_from_fwd(pf, C, Cg), want)
+        assert torch.equal(lp.gconv_w_from_dgrad(pd, C, Cg), want)
+
+
+def test_gconv_checks_pass_a_correct_launch_and_flag_a_wrong_one():
+    """check_gconv_fwd / dgrad / wgrad on the CPU with a stand-in launch that writes the float64 conv2d
+    result (rounded as the kernel stores it): all records pass; one element off by a bf16 step, or one
+    weight-gradient entry off by 1e-3 of its scale, fails."""
+    import gconv_ref as G
+    from cvlite import ops_nn
+    for (B, H, W, C, Cg, s) in [(2, 9, 7, 64, 4, 1), (3, 8, 10, 32, 32, 2)]:
+        inp = G.make_inputs("random", B, H, W, C, Cg, s, seed=5)
+        x, w, dy = inp["x"], inp["w"], inp["dy"]
+        pf, pd = lp.gconv_pack_ref(w, Cg)
+        xd = x.double().permute(0, 3, 1, 2).requires_grad_()
+        wd = w.to(torch.bfloat16).double().requires_grad_()
+        y64 = F.conv2d(F.pad(xd, (1, 1, 1, 1)), wd.permute(3, 2, 0, 1), None, s, groups=C // Cg)
+        gx, gw = torch.autograd.grad(y64, (xd, wd), dy.double().permute(0, 3, 1, 2))
+        y64, gx = y64.detach().permute(0, 2, 3, 1), gx.permute(0, 2, 3, 1)
+        for wrong in (False, True):
+            p = lp.LaunchParity(imgs=2)
+            p.nn = ops_nn
+
+            def fwd(x_, wf_, y_, Cg_, s_, stats_):
+                y_.copy_(y64.to(torch.bfloat16))
+                if wrong:
+                    y_[B - 1, 2, 3, 5] = (y_[B - 1, 2, 3, 5].float() * (1 + 2.0 ** -6) + 1e-3).to(torch.bfloat16)
+
+            def dgrad(dy_, wd_, dx_, Cg_, s_, beta=0.0):
+                dx_.copy_((gx + beta * dx_.double()).to(torch.bfloat16))
+                if wrong:
+                    dx_[0, H - 1, W - 1, C - 1] = 0.0
+
+            def wgrad(x_, dy_, dw_, s_, beta=0.0):
+                dw_.copy_((gw + beta * dw_.double()).float())
+                if wrong:
+                    dw_[2, 2, Cg - 1, C - 1] += 1e-3 * float(gw.abs().mean())
+
+            lp.check_gconv_fwd(p, "gconv3x3_fwd", fwd, x, pf, torch.empty(y64.shape, dtype=torch.bfloat16), Cg, s)
+            lp.check_gconv_dgrad(p, "gconv3x3_dgrad", dgrad, dy, pd, inp["dx_old"].clone(), Cg, s, beta=1.0)
+            lp.check_gconv_wgrad(p, "gconv3x3_wgrad", wgrad, x, dy, inp["dw_old"].clone(), s, beta=2.0)
+            assert [r.what for r in p.records] == ["y", "dx", "dW"]
+            if wrong:
+                assert len(p.failures()) == 3, p.table()
+            else:
+                assert not p.failures(), p.table()
+                assert all(0 < r.err <= 1 for r in p.records)
+
+
 def test_bn_affine_mask_is_fma_exact():
     g = torch.Generator().manual_seed(2)
     z = torch.randn(4096, generator=g).to(torch.bfloat16)
