@@ -48,6 +48,13 @@ SIGNATURES = {
     "cvl_fcos_atss_workspace_size": (c_size_t, [c_int, c_int]),
     "cvl_fcos_atss_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_float, P, P, P, P, P,
                                      P, c_size_t, P]),
+    # Generalized Focal Loss (csrc/fcos_gfl.hip)
+    "cvl_fcos_gfl_norm_workspace_size": (c_size_t, [c_int, c_int]),
+    "cvl_fcos_gfl_norm": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "cvl_fcos_gfl_loss_workspace_size": (c_size_t, [c_int, c_int]),
+    "cvl_fcos_gfl_loss": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
+                                  c_float, P, P, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
+    "cvl_fcos_gfl_decode": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
     "cvl_fcos_decode": (c_int, [P, c_int, c_int, c_int, ctypes.c_double, P, P]),
     "cvl_fcos_v1_decode": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P]),
     "cvl_conv_igemm_workspace_size": (c_size_t, [P]),
@@ -261,7 +268,9 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_bn_backward_bits", "cvl_bn_backward_res_sums_bits", "cvl_bn_backward_res_sums_sc_bits",
          "cvl_bn_backward_sc_bits", "cvl_conv_wgrad_plan", "cvl_conv_wgrad_batch_plan", "cvl_conv_igemm_res_relu",
          "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_", "cvl_eval_match_areas",
-         "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign", "cvl_gconv3x3_plan"}
+         "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign", "cvl_gconv3x3_plan",
+         "cvl_fcos_gfl_norm_workspace_size", "cvl_fcos_gfl_norm", "cvl_fcos_gfl_loss_workspace_size",
+         "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode"}
 
 
 def load():

@@ -139,6 +139,15 @@ def load_net_state(net, s):
     st = net.store
     names = [[k, int(o), int(n)] for k, (o, n, _) in st.offsets.items()]
     if [list(x) for x in s["names"]] != names:
+        # the box head is what FCOSNet(reg_max=...) changes: say so instead of a bare layout mismatch
+        key = "reg_output_1/kernel"
+        have = {x[0]: int(x[2]) for x in s["names"]}
+        want = {x[0]: x[2] for x in names}
+        if key in have and key in want and have[key] != want[key]:
+            per = 9 * 256
+            raise ValueError("checkpoint box head has %d outputs, this model's has %d (reg_max=%r): a checkpoint "
+                             "loads only into a network built with the same reg_max"
+                             % (have[key] // per, want[key] // per, getattr(net, "reg_max", None)))
         raise ValueError("checkpoint parameter layout does not match this model")
     st.flat.copy_(s["params"].to(st.flat.device))
     st.mom.copy_(s["momentum"].to(st.flat.device))

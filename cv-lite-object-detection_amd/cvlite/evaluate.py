@@ -515,7 +515,9 @@ def evaluate_fcos(model, samples, num_classes, batch_size=16, protocol="voc07", 
     Evaluator.add on its device outputs.  detect_kwargs: iou_thresh, cls_thresh, max_detections,
     max_total_size of image_detections.  fold_bn: the forwards run with the backbone's BatchNorms
     folded into its convs (folded once, before the first batch).  clamp_reg: image_detections' clamp of
-    the box outputs at 0 (networks trained with the FCOS papers' recipe).  Returns Evaluator.result()."""
+    the box outputs at 0 (networks trained with the FCOS papers' recipe).  A network built with reg_max
+    (Generalized Focal Loss) is decoded through its distributions, as image_detections does.  Returns
+    Evaluator.result()."""
     from .infer_fcos import image_detections
     ev = Evaluator(num_classes, protocol, iou_thresholds=iou_thresholds, max_dets=max_dets, area_ranges=area_ranges)
     for imgs, gt, ids, real, extra in _sample_batches(samples, batch_size, shard, areas=area_ranges is not None):

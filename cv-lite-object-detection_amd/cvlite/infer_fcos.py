@@ -24,13 +24,21 @@ CombinedNonMaxSuppression = collections.namedtuple(
 
 
 def detect_from_outputs(reg, cls, shapes, num_classes, center=False, iou_thresh=0.5, cls_thresh=0.05,
-                        max_detections=100, max_total_size=100, strides=STRIDES, clamp_reg=False):
+                        max_detections=100, max_total_size=100, strides=STRIDES, clamp_reg=False, reg_max=None):
     """Batched device form over the fused FCOS head outputs: reg [B,P,>=5] (t, b, l, r,
     centerness), cls [B,P,>=C] fp32, level shapes [(h, w)] x 5 (level-major rows).
     clamp_reg (cvlite extension): the four box columns are clamped at 0 first, on a copy -- what the
-    loss of the FCOS papers' recipe (ops_targets.fcos_paper_loss) trains the head outputs under."""
+    loss of the FCOS papers' recipe (ops_targets.fcos_paper_loss) trains the head outputs under.
+    reg_max (cvlite extension): reg holds the 4 (reg_max + 1) distribution logits of a Generalized Focal
+    Loss head; the distances are their expectations (ops_targets.fcos_gfl_decode into a [B,P,8] buffer)
+    and the score is the class score alone, so center must be False."""
     _lib.require_cuda(reg, cls)
-    if clamp_reg:
+    if reg_max is not None:
+        if center:
+            raise ValueError("a Generalized Focal Loss head has no centerness: center must be False")
+        from .ops_targets import fcos_gfl_decode
+        reg = fcos_gfl_decode(reg.contiguous(), reg_max)       # >= 0: nothing left to clamp
+    elif clamp_reg:
         reg = reg.clone()
         reg[..., :4].clamp_(min=0)
     B, P = int(reg.shape[0]), int(reg.shape[1])
@@ -60,7 +68,8 @@ def image_detections(image, model, num_classes, center=False, iou_thresh=0.5, cl
     [B,H,W,3] / [H,W,3] fp32 (already resized and scaled to [-1, 1]).  fold_bn (cvlite extension): run
     the forward with the backbone's BatchNorms folded into its convs (FPNDetector.fold_bn; ResNet
     backbones, bf16) -- the same map up to bf16 rounding, without the BN passes.  clamp_reg: detect_from_outputs'
-    clamp of the box outputs at 0 (networks trained with the FCOS papers' recipe)."""
+    clamp of the box outputs at 0 (networks trained with the FCOS papers' recipe).  A network built with
+    reg_max (Generalized Focal Loss) is decoded through its distributions: detect_from_outputs' reg_max."""
     net = getattr(model, "net", model)
     x = torch.as_tensor(image, dtype=torch.float32, device="cuda")
     if x.dim() == 3:
@@ -69,4 +78,4 @@ def image_detections(image, model, num_classes, center=False, iou_thresh=0.5, cl
     shapes, _, _ = net.layout(B, H, W)
     reg, cls = net.forward(x.contiguous(), train=False, folded=bool(fold_bn))
     return detect_from_outputs(reg, cls, shapes, num_classes, center, iou_thresh, cls_thresh, max_detections,
-                               max_total_size, clamp_reg=clamp_reg)
+                               max_total_size, clamp_reg=clamp_reg, reg_max=getattr(net, "reg_max", None))

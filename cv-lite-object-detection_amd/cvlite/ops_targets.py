@@ -227,6 +227,85 @@ def fcos_atss_assign(boxes, nbox, img_dim, pad_hw, num_classes, strides=FCOS_STR
     return (out, num_targets) + cand if return_candidates else (out, num_targets)
 
 
+# ---- Generalized Focal Loss (cvlite extension; include/cvlite.h states the rule) -------------------
+def _gfl_rows(reg_pred, cls_pred, targets, num_classes):
+    B, P = int(targets.shape[0]), int(targets.shape[1])
+    assert reg_pred.shape[:2] == (B, P) and cls_pred.shape[:2] == (B, P)
+    assert reg_pred.dtype == torch.float32 and cls_pred.dtype == torch.float32 and targets.dtype == torch.float32
+    assert reg_pred.is_contiguous() and cls_pred.is_contiguous() and targets.is_contiguous()
+    assert int(targets.shape[2]) == 5 + num_classes
+    return B, P
+
+
+def fcos_gfl_norm(cls_pred, targets, num_classes, out=None):
+    """norm [B,2] f32 = (number of positive cells, sum over them of sigmoid(max class logit)) per image
+    (cvl_fcos_gfl_norm); cls_pred [B,P,ld_cls>=C] f32, targets [B,P,5+C] f32.  The divisors of
+    fcos_gfl_loss; it needs the class outputs, so it runs after the forward."""
+    _lib.require_cuda(cls_pred, targets)
+    B, P = int(targets.shape[0]), int(targets.shape[1])
+    assert cls_pred.shape[:2] == (B, P) and cls_pred.dtype == torch.float32
+    assert targets.dtype == torch.float32 and int(targets.shape[2]) == 5 + num_classes
+    if out is None:
+        out = torch.empty((B, 2), device=targets.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, 2) and out.dtype == torch.float32 and out.is_contiguous()
+    ws = torch.empty(int(_lib.load().cvl_fcos_gfl_norm_workspace_size(B, P)), device=targets.device,
+                     dtype=torch.uint8)
+    _lib.call("cvl_fcos_gfl_norm", ptr(cls_pred), int(cls_pred.shape[2]), ptr(targets), B, P, int(num_classes),
+              ptr(out), ptr(ws), ws.numel(), _lib.stream())
+    return out
+
+
+def fcos_gfl_loss(reg_pred, cls_pred, targets, num_classes, reg_max, norm=None, grad_scale=1.0, with_grad=True,
+                  grad_dtype=torch.float32, d_reg=None, d_cls=None, beta=2.0, box_weight=2.0, dfl_weight=0.25,
+                  losses=None):
+    """Fused Generalized Focal Loss, forward and backward (cvl_fcos_gfl_loss): Quality Focal Loss on the
+    class logits with the decoded box's IoU as the positives' target / N, GIoU on the expectations of the
+    per-side distributions and Distribution Focal Loss, both weighted by sigmoid(max class logit) /
+    its sum, with (N, sum) = norm [B,2] as fcos_gfl_norm returns it (None: plain sums).
+    reg_pred [B,P,ld_reg>=4(reg_max+1)] f32 (side-major: top, bottom, left, right; reg_max+1 bins each),
+    cls_pred [B,P,ld_cls>=C] f32, targets [B,P,5+C] f32 (fcos_atss_assign / fcos_paper_assign).
+    Returns (losses [B,3] f32 = (qfl, box, dfl) per image, d_reg, d_cls)."""
+    _lib.require_cuda(reg_pred, cls_pred, targets)
+    B, P = _gfl_rows(reg_pred, cls_pred, targets, num_classes)
+    dev = targets.device
+    if norm is not None:
+        _lib.require_cuda(norm)
+        assert tuple(norm.shape) == (B, 2) and norm.dtype == torch.float32 and norm.is_contiguous()
+    if losses is None:
+        losses = torch.empty((B, 3), device=dev, dtype=torch.float32)
+    assert losses.shape == (B, 3) and losses.dtype == torch.float32 and losses.is_contiguous()
+    ws = torch.empty(int(_lib.load().cvl_fcos_gfl_loss_workspace_size(B, P)), device=dev, dtype=torch.uint8)
+    if with_grad:
+        if d_reg is None:
+            d_reg = torch.empty((B, P, reg_pred.shape[2]), device=dev, dtype=grad_dtype)
+        if d_cls is None:
+            d_cls = torch.empty((B, P, cls_pred.shape[2]), device=dev, dtype=grad_dtype)
+    for d in (d_reg, d_cls):
+        assert d is None or (d.shape[:2] == (B, P) and d.is_contiguous() and d.dtype in (torch.float32, torch.bfloat16))
+    dt = lambda t: 0 if t is None or t.dtype == torch.float32 else 1  # noqa: E731
+    _lib.call("cvl_fcos_gfl_loss", ptr(reg_pred), int(reg_pred.shape[2]), ptr(cls_pred), int(cls_pred.shape[2]),
+              ptr(targets), ptr(norm), B, P, int(num_classes), int(reg_max), float(grad_scale), float(beta),
+              float(box_weight), float(dfl_weight), ptr(losses), ptr(d_reg),
+              int(d_reg.shape[2]) if d_reg is not None else 0, dt(d_reg), ptr(d_cls),
+              int(d_cls.shape[2]) if d_cls is not None else 0, dt(d_cls), ptr(ws), ws.numel(), _lib.stream())
+    return losses, d_reg, d_cls
+
+
+def fcos_gfl_decode(reg_pred, reg_max, out=None):
+    """The distances of a GFL box head (cvl_fcos_gfl_decode): reg_pred [..., ld_reg>=4(reg_max+1)] f32 ->
+    [..., 8] f32 with columns 0..3 = the expectations of the (top, bottom, left, right) distributions in
+    stride units and columns 4..7 zero: the box rows that cvl_fcos_detect reads with center = 0."""
+    _lib.require_cuda(reg_pred)
+    assert reg_pred.dtype == torch.float32 and reg_pred.dim() >= 2
+    rows = int(reg_pred.numel() // reg_pred.shape[-1])
+    if out is None:
+        out = torch.empty(tuple(reg_pred.shape[:-1]) + (8,), device=reg_pred.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and int(out.numel() // out.shape[-1]) == rows
+    _lib.call("cvl_fcos_gfl_decode", ptr(reg_pred), int(reg_pred.shape[-1]), rows, int(reg_max), ptr(out),
+              int(out.shape[-1]), _lib.stream())
+    return out
+
+
 def _boxes_args(boxes, nbox, img_dim):
     _lib.require_cuda(boxes, nbox, img_dim)
     assert boxes.dtype == torch.float32 and nbox.dtype == torch.int32 and img_dim.dtype == torch.float32

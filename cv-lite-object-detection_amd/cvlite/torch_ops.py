@@ -23,6 +23,12 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
   torch.ops.cvlite.fcos_atss_assign(boxes, nbox, img_dim, pad_h, pad_w, C, topk, anchor_scale)
                                                           ATSS targets (cvlite extension) for the
                                                           same fcos_target_norm / fcos_paper_loss
+  torch.ops.cvlite.fcos_gfl_norm(cls, targets, C),
+  torch.ops.cvlite.fcos_gfl_loss(reg, cls, targets, norm, C, reg_max, beta, box_weight, dfl_weight),
+  torch.ops.cvlite.fcos_gfl_decode(reg, reg_max)          Generalized Focal Loss on a distribution box
+                                                          head (cvlite extension): [B, 3] = (qfl, box,
+                                                          dfl) with autograd as fcos_loss, and the
+                                                          expected distances for inference
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -337,6 +343,74 @@ def _paper_loss_backward(ctx, g):
 fcos_paper_loss.register_autograd(_paper_loss_backward, setup_context=_paper_loss_setup)
 
 
+# ---- Generalized Focal Loss (cvlite extension) --------------------------------------------------------
+@torch.library.custom_op("cvlite::fcos_gfl_norm", mutates_args=(), device_types="cuda")
+def fcos_gfl_norm(cls: torch.Tensor, targets: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """cls [B,P,>=C] fp32, targets [B,P,5+C] -> [B,2] = (number of positive cells, sum over them of
+    sigmoid(max class logit)).  No gradient flows through it (the loss treats its divisors as constants)."""
+    return ot.fcos_gfl_norm(cls.contiguous(), targets.contiguous(), num_classes)
+
+
+@fcos_gfl_norm.register_fake
+def _(cls, targets, num_classes):
+    return targets.new_empty((targets.shape[0], 2))
+
+
+@torch.library.custom_op("cvlite::fcos_gfl_loss", mutates_args=(), device_types="cuda")
+def fcos_gfl_loss(reg: torch.Tensor, cls: torch.Tensor, targets: torch.Tensor, norm: Optional[torch.Tensor],
+                  num_classes: int, reg_max: int, beta: float = 2.0, box_weight: float = 2.0,
+                  dfl_weight: float = 0.25) -> torch.Tensor:
+    """Generalized Focal Loss per image: reg [B,P,>=4(reg_max+1)] fp32, cls [B,P,>=C] fp32, targets
+    [B,P,5+C], norm [B,2] from fcos_gfl_norm (None: plain sums) -> [B,3] = (qfl, box, dfl)."""
+    losses, _, _ = ot.fcos_gfl_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), num_classes, reg_max,
+                                    norm=None if norm is None else norm.contiguous(), with_grad=False, beta=beta,
+                                    box_weight=box_weight, dfl_weight=dfl_weight)
+    return losses
+
+
+@fcos_gfl_loss.register_fake
+def _(reg, cls, targets, norm, num_classes, reg_max, beta=2.0, box_weight=2.0, dfl_weight=0.25):
+    return reg.new_empty((reg.shape[0], 3))
+
+
+def _gfl_loss_setup(ctx, inputs, output):
+    reg, cls, targets, norm, C, R, beta, wb, wd = inputs
+    ctx.save_for_backward(reg, cls, targets, norm)
+    ctx.args = (C, R, beta, wb, wd)
+
+
+def _gfl_loss_backward(ctx, g):
+    reg, cls, targets, norm = ctx.saved_tensors
+    C, R, beta, wb, wd = ctx.args
+    g = g.to(torch.float32)
+    run = lambda b, d: ot.fcos_gfl_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), C, R,  # noqa: E731
+                                        norm=None if norm is None else norm.contiguous(), grad_scale=1.0,
+                                        beta=beta, box_weight=b, dfl_weight=d)
+    # the kernel returns d(qfl + box + dfl); the box rows are linear in the two weights, so one call per
+    # term separates them: qfl -> class logits, box and dfl -> the distributions; padding columns get zero
+    _, d_box, d_cls = run(wb, 0.0)
+    _, d_dfl, _ = run(0.0, wd)
+    cscale = torch.zeros((reg.shape[0], 1, cls.shape[2]), dtype=torch.float32, device=reg.device)
+    cscale[:, 0, :C] = g[:, 0:1]
+    d_reg = d_box * g[:, 1].view(-1, 1, 1) + d_dfl * g[:, 2].view(-1, 1, 1)
+    return d_reg, d_cls * cscale, None, None, None, None, None, None, None
+
+
+fcos_gfl_loss.register_autograd(_gfl_loss_backward, setup_context=_gfl_loss_setup)
+
+
+@torch.library.custom_op("cvlite::fcos_gfl_decode", mutates_args=(), device_types="cuda")
+def fcos_gfl_decode(reg: torch.Tensor, reg_max: int) -> torch.Tensor:
+    """reg [B,P,>=4(reg_max+1)] fp32 -> [B,P,8] fp32: columns 0..3 the expected (top, bottom, left, right)
+    distances in stride units, columns 4..7 zero (inference; no gradient)."""
+    return ot.fcos_gfl_decode(reg.contiguous(), reg_max)
+
+
+@fcos_gfl_decode.register_fake
+def _(reg, reg_max):
+    return reg.new_empty(tuple(reg.shape[:-1]) + (8,))
+
+
 # ---- optimizer -----------------------------------------------------------------------------------
 @torch.library.custom_op("cvlite::sgd_clip_", mutates_args=("w", "v"), device_types="cuda")
 def sgd_clip_(w: torch.Tensor, g: torch.Tensor, v: torch.Tensor, lr: torch.Tensor, momentum: float, inv_bs: float,
@@ -364,7 +438,9 @@ class NetFunction(torch.autograd.Function):
     def backward(ctx, g_reg, g_cls):
         net = ctx.net
         B, P = ctx.shapes[0][0], ctx.shapes[0][1]
-        d_reg = torch.zeros((B, P, 32), dtype=BF16, device=net.device)
+        # (a Generalized Focal Loss head, FCOSNet(reg_max=R), is wider: its own padding)
+        reg_w = net.reg_heads[0].cout_pad if getattr(net, "reg_max", None) is not None else 32
+        d_reg = torch.zeros((B, P, reg_w), dtype=BF16, device=net.device)
         d_cls = torch.zeros((B, P, net.cls_ld), dtype=BF16, device=net.device)
         if g_reg is not None:
             d_reg[..., :g_reg.shape[2]] = g_reg.to(BF16)

@@ -35,11 +35,30 @@ class SGD(object):
         self.momentum = float(momentum)
 
 
+TARGET_KINDS = ("fcos", "center", "center_v1", "paper", "atss", "gfl")
+
+
+def check_recipe(net, targets):
+    """The network / targets pairs the trainers take (ValueError otherwise, before any device work):
+    "paper", "atss" and "gfl" need the FCOS network, "gfl" one built with reg_max, and a network built
+    with reg_max trains with "gfl" only (every other loss reads a 5-output box head)."""
+    if targets not in TARGET_KINDS:
+        raise ValueError("targets must be 'fcos', 'center', 'center_v1', 'paper', 'atss' or 'gfl'")
+    if targets in ("paper", "atss", "gfl") and hasattr(net, "cen_heads"):
+        raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
+    reg_max = getattr(net, "reg_max", None)
+    if targets == "gfl" and reg_max is None:
+        raise ValueError("targets='gfl' needs a network built with reg_max (FCOSNet(..., reg_max=R))")
+    if targets != "gfl" and reg_max is not None:
+        raise ValueError("a network built with reg_max=%r trains with targets='gfl', not %r" % (reg_max, targets))
+
+
 class FCOSTrainer(GraphStepper):
     def __init__(self, net, batch_size, image_hw, n_max=16, init_lr=5e-4, min_lr=1e-5, decay_step=1000,
                  decay_rate=0.9, momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0,
                  world=1, use_graph=True, st_step=0, targets="fcos", center_only=True, optimizer=None,
-                 max_decays=None, center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0):
+                 max_decays=None, center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0, gfl_beta=2.0,
+                 gfl_box_weight=2.0, gfl_dfl_weight=0.25):
         self.net = net
         # optimizer: None or SGD -> Keras SGD with `momentum` (train_fcos.py:284-285); an Adam
         # (cvlite.train_centernet.Adam, the tf.optimizers.Adam() stand-in) -> Keras Adam, what the
@@ -72,12 +91,14 @@ class FCOSTrainer(GraphStepper):
         # "atss" (cvlite extension): fcos_atss_assign (the atss_topk nearest grid points per level, anchors
         # of side atss_scale * stride, IoU threshold mean + std per box) in front of the same
         # fcos_target_norm and fcos_paper_loss
-        if targets not in ("fcos", "center", "center_v1", "paper", "atss"):
-            raise ValueError("targets must be 'fcos', 'center', 'center_v1', 'paper' or 'atss'")
-        if targets in ("paper", "atss") and hasattr(net, "cen_heads"):
-            raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
+        # "gfl" (cvlite extension): Generalized Focal Loss on a network built with reg_max -- fcos_atss_assign,
+        # the forward, fcos_gfl_norm (it reads the class outputs, so it follows the forward) and
+        # fcos_gfl_loss (QFL with exponent gfl_beta, GIoU weighted gfl_box_weight, DFL weighted
+        # gfl_dfl_weight; per-image normalisation); losses columns are then (qfl, box, dfl)
+        check_recipe(net, targets)
         self.target_kind, self.center_only = targets, center_only
         self.atss_topk, self.atss_scale = int(atss_topk), float(atss_scale)
+        self.gfl = (float(gfl_beta), float(gfl_box_weight), float(gfl_dfl_weight))
         self.center_radius = float(center_radius)
         self.bounds = tuple(float(v) for v in (ot.FCOS_PAPER_BOUNDS if bounds is None else bounds))
         # the centre networks (cvlite.fcos_center_net): focal centerness from the cls-tower head in
@@ -97,10 +118,13 @@ class FCOSTrainer(GraphStepper):
         self.targets = torch.zeros((B, self.P, 5 + self.C), dtype=torch.float32, device=dev)
         self.ntgt = torch.zeros((B, 5), dtype=torch.int32, device=dev)
         act = net.store.act                   # bf16, or fp32 in the parity mode
-        self.d_reg = torch.zeros((B, self.P, 32), dtype=act, device=dev)
+        # the box head's gradient rows, as wide as the head's data-gradient pack (32 for the 5-output head)
+        self.d_reg = torch.zeros((B, self.P, net.reg_heads[0].cout_pad if hasattr(net, "reg_heads") else 32),
+                                 dtype=act, device=dev)
         self.d_cls = torch.zeros((B, self.P, net.cls_ld), dtype=act, device=dev)
         self.losses = torch.zeros((B, 3), dtype=torch.float32, device=dev)
-        self.norm = torch.zeros((B, 2), dtype=torch.float32, device=dev) if targets in ("paper", "atss") else None
+        self.norm = (torch.zeros((B, 2), dtype=torch.float32, device=dev) if targets in ("paper", "atss", "gfl")
+                     else None)
         # the heads' fp32 outputs, zeroed once (FCOSNet writes only the used columns; see
         # FCOSNet._heads_forward) -- lent to the network for the step's forward only
         self._head_out = ((torch.zeros((B, self.P, net.reg_ld), dtype=torch.float32, device=dev),
@@ -129,6 +153,10 @@ class FCOSTrainer(GraphStepper):
                                         topk=self.atss_topk, anchor_scale=self.atss_scale, out=self.targets,
                                         num_targets=self.ntgt)
             ot.fcos_target_norm(tg, self.C, out=self.norm)
+        elif self.target_kind == "gfl":           # its norm reads the class outputs: after the forward
+            tg, _ = ot.fcos_atss_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
+                                        topk=self.atss_topk, anchor_scale=self.atss_scale, out=self.targets,
+                                        num_targets=self.ntgt)
         elif self.target_kind == "center":
             tg, _ = ot.fcos_center_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
                                           center_only=self.center_only, out=self.targets, num_targets=self.ntgt)
@@ -144,7 +172,12 @@ class FCOSTrainer(GraphStepper):
         finally:
             self.net.head_out = None
         self.outputs = (reg, cls)                 # head outputs of the last step (graph memory)
-        if self.target_kind in ("paper", "atss"):
+        if self.target_kind == "gfl":
+            beta, w_box, w_dfl = self.gfl
+            ot.fcos_gfl_norm(cls, tg, self.C, out=self.norm)
+            ot.fcos_gfl_loss(reg, cls, tg, self.C, self.net.reg_max, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
+                             d_cls=self.d_cls, beta=beta, box_weight=w_box, dfl_weight=w_dfl, losses=self.losses)
+        elif self.target_kind in ("paper", "atss"):
             ot.fcos_paper_loss(reg, cls, tg, self.C, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
                                d_cls=self.d_cls, losses=self.losses)
         else:
@@ -197,7 +230,7 @@ class JitterFCOSTrainer(object):
     def __init__(self, net, batch_size, n_max=16, init_lr=5e-4, min_lr=1e-5, decay_step=1000, decay_rate=0.9,
                  momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0, st_step=0, use_graph=True,
                  max_buckets=12, world=1, optimizer=None, max_decays=None, targets="fcos", center_radius=1.5,
-                 bounds=None, atss_topk=9, atss_scale=8.0):
+                 bounds=None, atss_topk=9, atss_scale=8.0, gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25):
         # world > 1: data-parallel (dist.py) -- each rank runs its own bs images through its buckets,
         # the summed gradient is all-reduced (one bucketed SUM over RCCL) before the shared update
         # with 1 / (world * bs); the buckets differ per rank, so there is no overlap with the backward
@@ -207,12 +240,13 @@ class JitterFCOSTrainer(object):
         self.max_decays = max_decays
         self.sched = (init_lr, min_lr, decay_rate, decay_step)
         self.reg_type, self.use_graph, self.max_buckets = reg_type, use_graph, max_buckets
-        # targets / center_radius / bounds / atss_topk / atss_scale: forwarded to every bucket's FCOSTrainer
-        # ("paper": the FCOS papers' recipe; "atss": ATSS targets under the same loss)
-        if targets in ("paper", "atss") and hasattr(net, "cen_heads"):
-            raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
+        # targets / center_radius / bounds / atss_topk / atss_scale / gfl_*: forwarded to every bucket's
+        # FCOSTrainer ("paper": the FCOS papers' recipe; "atss": ATSS targets under the same loss; "gfl":
+        # Generalized Focal Loss on ATSS targets, a network built with reg_max)
+        check_recipe(net, targets)
         self.bucket_kw = dict(targets=targets, center_radius=center_radius, bounds=bounds, atss_topk=atss_topk,
-                              atss_scale=atss_scale)
+                              atss_scale=atss_scale, gfl_beta=gfl_beta, gfl_box_weight=gfl_box_weight,
+                              gfl_dfl_weight=gfl_dfl_weight)
         self.weight_decay = float(weight_decay)
         self.l2 = nn.L2Reg(net.store) if self.weight_decay > 0.0 else None
         dev = net.device
@@ -377,7 +411,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
           init_lr=1.0e-3, min_lr=1.0e-5, decay_step=1000, decay_rate=0.99, display_step=50, step_save=100,
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
           max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07",
-          eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0):
+          eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0,
+          gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -414,7 +449,11 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       gradient divisor stays 1 / (batch_size * world)), and "Average Objs" then counts positive cells;
       the eval_data hook evaluates with the box outputs clamped at 0 (clamp_reg=True), as that loss
       trains them.  "atss" = ATSS targets (FCOSTrainer(targets="atss", atss_topk, atss_scale)) under the
-      same loss, divisor, "Average Objs" and clamped evaluation.
+      same loss, divisor, "Average Objs" and clamped evaluation.  "gfl" = Generalized Focal Loss
+      (FCOSTrainer(targets="gfl", atss_topk, atss_scale, gfl_beta, gfl_box_weight, gfl_dfl_weight)) on a
+      network built with reg_max: ATSS targets, the same divisor and "Average Objs"; the printed
+      "Cls / Reg / Cen" averages are then the (qfl, box, dfl) columns, and the eval_data hook evaluates
+      through the distribution decode (evaluate_fcos reads reg_max from the network).
     The reference's thermal "Cooling GPU" sleep runs only with CVL_COOLING=1.  Returns None."""
     from . import checkpoint as ck
     import torch.distributed as tdist
@@ -432,15 +471,20 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
         raise ValueError("train_data holds %d samples, fewer than world * batch_size" % n_data)
     say = print if rank == 0 else (lambda *a, **k: None)
     momentum = float(getattr(optimizer, "momentum", 0.9))
-    if recipe not in ("reference", "paper", "atss"):
-        raise ValueError("recipe must be 'reference', 'paper' or 'atss', not %r" % (recipe,))
+    if recipe not in ("reference", "paper", "atss", "gfl"):
+        raise ValueError("recipe must be 'reference', 'paper', 'atss' or 'gfl', not %r" % (recipe,))
     if recipe == "atss" and hasattr(net, "cen_heads"):
         raise ValueError("recipe='atss' needs the FCOS network, not a centre variant")
+    if recipe == "gfl" or getattr(net, "reg_max", None) is not None:
+        check_recipe(net, "gfl" if recipe == "gfl" else "fcos" if recipe == "reference" else recipe)
     recipe_kw = {}
     if recipe == "paper":
         recipe_kw = dict(targets="paper", center_radius=center_radius, bounds=bounds)
     elif recipe == "atss":
         recipe_kw = dict(targets="atss", atss_topk=atss_topk, atss_scale=atss_scale)
+    elif recipe == "gfl":
+        recipe_kw = dict(targets="gfl", atss_topk=atss_topk, atss_scale=atss_scale, gfl_beta=gfl_beta,
+                         gfl_box_weight=gfl_box_weight, gfl_dfl_weight=gfl_dfl_weight)
     if raw:          # reference-format samples: per-image jittered sizes, shape-bucketed step
         n_max = max(16, max(len(s["objects"]["label"]) for s in train_data))
         trainer = JitterFCOSTrainer(net, batch_size, n_max=n_max, init_lr=init_lr, min_lr=min_lr,

@@ -207,6 +207,62 @@ int cvl_fcos_atss_assign(const float* boxes, const int32_t* nbox, const float* i
                          cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Generalized Focal Loss for the FCOS head (Li et al., NeurIPS 2020, "Generalized Focal Loss: Learning
+ * Qualified and Distributed Bounding Boxes for Dense Object Detection"): an extension beyond the
+ * reference, trained on the targets of cvl_fcos_atss_assign (or cvl_fcos_paper_assign).  The
+ * centerness output is gone: the class target of a positive is the IoU of its decoded box (Quality
+ * Focal Loss), and each box side is a discrete distribution over R + 1 bins (Distribution Focal Loss)
+ * whose expectation is the distance.  Compiled without contraction; fp32 unless float64 is named.
+ *
+ * Layout as cvl_fcos_paper_loss except for the box rows: R = reg_max, 1 <= R <= 16; cls_pred
+ * [B][P][ld_cls >= C]; reg_pred [B][P][ld_reg >= 4(R+1)] with z[j][i] = reg_pred[.. + j*(R+1) + i], side
+ * j = 0..3 = (top, bottom, left, right) in the order of targets[0..3], bin i = 0..R in stride units;
+ * targets [B][P][5+C] as the assign entries write them (targets[4] is not read).  A cell is positive
+ * when max_c targets[5+c] >= 1.
+ *   every cell, every class c: s_c = sigmoid(x_c); y_c = q if the cell is positive and targets[5+c] >= 1,
+ *     else 0;  QFL_c = |y_c - s_c|^beta * (max(x_c,0) - x_c*y_c + log1p(exp(-|x_c|)))
+ *     (beta = 2 is evaluated as a product, other values through powf)
+ *   positive cells, all softmaxes max-subtracted: p[j] = softmax(z[j]), d_j = sum_i i*p[j][i], t_j =
+ *     targets[j]; th = t0+t1, tw = t2+t3, ph = d0+d1, pw = d2+d3,
+ *     I = (min(t0,d0)+min(t1,d1)) (min(t2,d2)+min(t3,d3)), U = th tw + ph pw - I + 1e-12,
+ *     E = (max(t0,d0)+max(t1,d1)) (max(t2,d2)+max(t3,d3)) + 1e-12, GIoU = I/U - (E - U)/E
+ *     (the expressions of cvl_fcos_paper_loss with d_j in the place of max(p_j, 0));
+ *     q = I/U and w = sigmoid(max_c x_c), BOTH constants for the gradient;
+ *     tc_j = fminf(fmaxf(t_j, 0), (float)R - 0.1f), yl = floorf(tc_j), wl = (yl + 1) - tc_j, wr = tc_j - yl,
+ *     dfl_cell = 0.25 * sum_j [wl*(lse(z[j]) - z[j][yl]) + wr*(lse(z[j]) - z[j][yl+1])]
+ *   per image, losses [B][3] = (qfl, box, dfl) with N = max(norm[b][0], 1), Wsum = max(norm[b][1], 1e-6f)
+ *     (null norm: N = Wsum = 1):  qfl = (1/N) sum_cells sum_c QFL_c;  box = (w_box/Wsum) sum_pos w*(1 - GIoU);
+ *     dfl = (w_dfl/Wsum) sum_pos w*dfl_cell.  The published values are beta = 2, w_box = 2, w_dfl = 0.25.
+ *   gradients = grad_scale * d(qfl + box + dfl)/d(pred): d_cls from QFL only, d_reg from box and DFL
+ *     only; non-positive cells get all-zero box rows (their box logits are never read); the padding
+ *     columns of both gradient rows are zeroed.  d_reg / d_cls: fp32 (dtype 0) or bf16 (1), or null for
+ *     forward only.
+ * Per-image sums are float64 per-tile partials and a fixed-order second pass: a call is bit-identical
+ * from run to run.  The normalisation is per image (the published code normalises over the batch).
+ *
+ * cvl_fcos_gfl_norm: norm[b] = (number of positive cells, sum over them of sigmoid(max_c x_c)), summed
+ * in float64 in a fixed order and stored as fp32; it needs the class outputs, so it runs after the
+ * forward.  workspace >= cvl_fcos_gfl_norm_workspace_size(B, P) bytes.
+ * cvl_fcos_gfl_loss: workspace >= cvl_fcos_gfl_loss_workspace_size(B, P) bytes.
+ * cvl_fcos_gfl_decode: out[row][0..3] = d_j of reg_pred row `row` (rows = B*P), columns 4..ld_out-1
+ * zero, ld_out >= 8: what cvl_fcos_detect with center = 0 reads as (t, b, l, r).
+ * Arguments out of range (R outside 1..16, an ld too small, beta < 0, a dtype other than 0 / 1, a
+ * workspace too small) return the invalid-argument status and write nothing.  All three are graph-safe:
+ * no host synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------------- */
+size_t cvl_fcos_gfl_norm_workspace_size(int B, int P);
+int cvl_fcos_gfl_norm(const float* cls_pred, int ld_cls, const float* targets, int B, int P, int num_classes,
+                      float* norm, void* workspace, size_t workspace_bytes, cvl_stream_t stream);
+size_t cvl_fcos_gfl_loss_workspace_size(int B, int P);
+int cvl_fcos_gfl_loss(const float* reg_pred, int ld_reg, const float* cls_pred, int ld_cls,
+                      const float* targets, const float* norm, int B, int P, int num_classes, int reg_max,
+                      float grad_scale, float beta, float w_box, float w_dfl, float* losses, void* d_reg,
+                      int ld_dreg, int dreg_dtype, void* d_cls, int ld_dcls, int dcls_dtype, void* workspace,
+                      size_t workspace_bytes, cvl_stream_t stream);
+int cvl_fcos_gfl_decode(const float* reg_pred, int ld_reg, int rows, int reg_max, float* out, int ld_out,
+                        cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Segmented implicit-GEMM convolution (bf16 MFMA, fp32 accumulate).  Replaces every Conv2D of
  * the reference graphs (Keras ResNet50 backbone; FCOS/fcos.py:49-101 FPN, towers and heads;
  * RetinaNet/retinanet_module.py:74-148) forward (mode FWD) and backward-input (mode DGRAD).
