@@ -11,6 +11,7 @@
 // Index/target kernels follow the reference's fp32 operation sequences exactly (this file is
 // compiled with -ffp-contract=off) and keep float64 where the reference computes in float64.
 #include "cvl_common.h"
+#include "smooth_l1.h"          // sl1_elem
 
 namespace {
 
@@ -336,15 +337,6 @@ __device__ __forceinline__ float focal_elem(float y, float x, float* g) {
   const float nlp = L - fminf(x, 0.f), nlq = L + fmaxf(x, 0.f);
   *g = -y * 0.25f * q1 * q1 * (2.0f * p1 * nlp + q1) + (1.0f - y) * 0.75f * p1 * p1 * (2.0f * q1 * nlq + p1);
   return y * 0.25f * q1 * q1 * nlp + (1.0f - y) * 0.75f * p1 * p1 * nlq;
-}
-
-// one (discontinuous, Q8) smooth-L1 element, delta 1: returns the loss, *g = d loss / d pred
-__device__ __forceinline__ float sl1_elem(float t, float x, float* g) {
-  const float d = t - x;
-  const float ad = fabsf(d);
-  if (ad < 1.0f) { *g = -d; return 0.5f * d * d; }
-  *g = d > 0.f ? -1.0f : (d < 0.f ? 1.0f : 0.0f);
-  return ad;
 }
 
 __global__ void __launch_bounds__(NT) det_loss_kernel(DetLossArgs a) {

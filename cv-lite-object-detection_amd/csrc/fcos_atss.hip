@@ -15,6 +15,7 @@
 //   write    per 256-cell tile: decode the winner, recompute its values, stage the [cells, 5+C] slab
 //            in LDS and store it coalesced; positives per level by ballots and integer atomics
 // Integer max and integer add are order-independent, so the result is bit-identical run to run.
+#include "atss_select.h"
 #include "cvl_common.h"
 
 #include <math.h>
@@ -25,8 +26,6 @@ constexpr int kMaxBoxes = 256;   // per image
 constexpr int kMaxTopk = 16;
 constexpr int kThreads = 256;
 constexpr int kLevels = 5;
-constexpr unsigned kNanKey = 0x7FC00000u;     // orders a NaN distance above +inf
-constexpr int kCache = 18;                    // keys per lane of the widest window: ceil(33 * 33 / 64)
 
 struct AtssArgs {
   const float* boxes;
@@ -63,123 +62,6 @@ __device__ __forceinline__ AtssBox load_box(const float* r, float H, float W, in
   return bx;
 }
 
-// a squared distance (>= 0, or NaN) as the unsigned integer that orders as the rule does
-__device__ __forceinline__ unsigned ord_bits(float v) { return v != v ? kNanKey : __float_as_uint(v); }
-
-// Wave minimum by DPP moves (register-to-register, no LDS round trip as a shuffle has; the select
-// rounds are a chain of these): a scan within each row of 16 lanes by row_shr 1, 2, 4, 8, then
-// row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3 leave the minimum in lane 63.  A
-// lane without a source takes the identity, all ones.  Every lane of the wave must be active.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_or_ones(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned long long min_step_u64(unsigned long long v) {
-  const unsigned lo = dpp_or_ones<CTRL, ROW_MASK>((unsigned)v);
-  const unsigned hi = dpp_or_ones<CTRL, ROW_MASK>((unsigned)(v >> 32));
-  const unsigned long long u = ((unsigned long long)hi << 32) | lo;
-  return u < v ? u : v;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned min_step_u32(unsigned v) {
-  const unsigned u = dpp_or_ones<CTRL, ROW_MASK>(v);
-  return u < v ? u : v;
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-  v = min_step_u64<0x111, 0xF>(v);      // row_shr:1
-  v = min_step_u64<0x112, 0xF>(v);      // row_shr:2
-  v = min_step_u64<0x114, 0xF>(v);      // row_shr:4
-  v = min_step_u64<0x118, 0xF>(v);      // row_shr:8
-  v = min_step_u64<0x142, 0xA>(v);      // row_bcast:15
-  v = min_step_u64<0x143, 0xC>(v);      // row_bcast:31
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-  v = min_step_u32<0x111, 0xF>(v);
-  v = min_step_u32<0x112, 0xF>(v);
-  v = min_step_u32<0x114, 0xF>(v);
-  v = min_step_u32<0x118, 0xF>(v);
-  v = min_step_u32<0x142, 0xA>(v);
-  v = min_step_u32<0x143, 0xC>(v);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// k rounds of a wave arg-min of (d2 bits << 32 | row-major cell index) over the rows r0..r1, columns
-// c0..c1 of a level; round j's key lands in lane j's `mine`.  The keys are distinct, so round j takes
-// the smallest key above round j-1's.  Returns the last round's key.
-__device__ __forceinline__ unsigned long long select_rounds(int k, int r0, int r1, int c0, int c1, int Ws, float sf,
-                                                            float yc, float xc, int lane,
-                                                            unsigned long long& mine) {
-  const int wc = c1 - c0 + 1;
-  const int nwin = (r1 - r0 + 1) * wc;
-  auto key_of = [&](int e) {
-    const int cy = r0 + e / wc, cx = c0 + e % wc;
-    const float gy = ((float)cy + 0.5f) * sf, gx = ((float)cx + 0.5f) * sf;
-    const float dy = gy - yc, dx = gx - xc;
-    const float d2 = dy * dy + dx * dx;
-    return ((unsigned long long)ord_bits(d2) << 32) | (unsigned)(cy * Ws + cx);
-  };
-  unsigned long long last = 0;
-  if (nwin <= 64 * kCache) {
-    // the window's keys are computed once and held in registers (kCache per lane)
-    const int ne = (nwin + 63) / 64;
-    unsigned long long kk[kCache];
-#pragma unroll
-    for (int u = 0; u < kCache; ++u) {
-      const int e = u * 64 + lane;
-      kk[u] = (u < ne && e < nwin) ? key_of(e) : ~0ull;
-    }
-    for (int j = 0; j < k; ++j) {
-      unsigned long long best = ~0ull;
-#pragma unroll
-      for (int u = 0; u < kCache; ++u)
-        if (u < ne) {
-          const unsigned long long key = kk[u];
-          if ((j == 0 || key > last) && key < best) best = key;
-        }
-      best = wave_min_u64(best);
-      if (lane == j) mine = best;
-      last = best;
-    }
-    return last;
-  }
-  // a larger range (the whole of a large level): the keys are computed again in every round
-  for (int j = 0; j < k; ++j) {
-    unsigned long long best = ~0ull;
-    for (int e = lane; e < nwin; e += 64) {
-      const unsigned long long key = key_of(e);
-      if ((j == 0 || key > last) && key < best) best = key;
-    }
-    best = wave_min_u64(best);
-    if (lane == j) mine = best;
-    last = best;
-  }
-  return last;
-}
-
-// The smallest squared distance along one axis over the cells outside [w0, w1] (`out`) and over all
-// n cells (`all`), as ord_bits.
-__device__ __forceinline__ void axis_minima(int n, int w0, int w1, float sf, float c, int lane, unsigned& out,
-                                            unsigned& all) {
-  unsigned mo = kNanKey, ma = kNanKey;
-  for (int q = lane; q < n; q += 64) {
-    const float g = ((float)q + 0.5f) * sf;
-    const float d = g - c;
-    const unsigned v = ord_bits(d * d);
-    ma = v < ma ? v : ma;
-    if (q < w0 || q > w1) mo = v < mo ? v : mo;
-  }
-  out = wave_min_u32(mo);
-  all = wave_min_u32(ma);
-}
-
 __global__ void __launch_bounds__(64 * kLevels) fcos_atss_select_kernel(AtssArgs a) {
   const int b = blockIdx.y, i = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
@@ -209,27 +91,9 @@ __global__ void __launch_bounds__(64 * kLevels) fcos_atss_select_kernel(AtssArgs
   const int Hs = a.Hs[lvl], Ws = a.Ws[lvl];
   const float sf = (float)a.strides[lvl];
   const int k = min(topk, Hs * Ws);
-  // the window: topk cells either side of the clamped cell of the centre (a NaN centre clamps to 0)
-  const int ry = (int)fminf(fmaxf(floorf(bx.yc / sf), 0.f), (float)(Hs - 1));
-  const int rx = (int)fminf(fmaxf(floorf(bx.xc / sf), 0.f), (float)(Ws - 1));
-  const int r0 = max(ry - topk, 0), r1 = min(ry + topk, Hs - 1);
-  const int c0 = max(rx - topk, 0), c1 = min(rx + topk, Ws - 1);
+  // the rounds run over the window of topk cells either side of the centre's cell, checked (atss_select.h)
   unsigned long long mine = 0;
-  unsigned long long kth = select_rounds(k, r0, r1, c0, c1, Ws, sf, bx.yc, bx.xc, lane, mine);
-  if (r0 > 0 || r1 < Hs - 1 || c0 > 0 || c1 < Ws - 1) {
-    // d2 = fl(a_r + b_s) is monotone in a_r = dy^2 and b_s = dx^2, so the smallest d2 outside the
-    // window is the smaller of fl(min a outside + min b) and fl(min a + min b outside).  Unless that
-    // is strictly above the k-th selected d2 (a far-off centre whose distances round together), the
-    // rounds run again over the whole level.
-    unsigned ao, aa, bo, ba;
-    axis_minima(Hs, r0, r1, sf, bx.yc, lane, ao, aa);
-    axis_minima(Ws, c0, c1, sf, bx.xc, lane, bo, ba);
-    const unsigned m1 = ord_bits(__uint_as_float(ao) + __uint_as_float(ba));
-    const unsigned m2 = ord_bits(__uint_as_float(aa) + __uint_as_float(bo));
-    const unsigned outside = m1 < m2 ? m1 : m2;
-    if (!(outside > (unsigned)(kth >> 32)))
-      kth = select_rounds(k, 0, Hs - 1, 0, Ws - 1, Ws, sf, bx.yc, bx.xc, lane, mine);
-  }
+  atss_select_cells(k, topk, Hs, Ws, sf, [sf](int q) { return ((float)q + 0.5f) * sf; }, bx.yc, bx.xc, lane, mine);
 
   // ---- anchor IoU of lane j's candidate ----------------------------------------------------------
   if (lane < topk) {

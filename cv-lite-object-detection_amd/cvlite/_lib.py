@@ -48,6 +48,13 @@ SIGNATURES = {
     "cvl_fcos_atss_workspace_size": (c_size_t, [c_int, c_int]),
     "cvl_fcos_atss_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_float, P, P, P, P, P,
                                      P, c_size_t, P]),
+    # ATSS for RetinaNet: compact targets and the normalised loss (csrc/retina_atss.hip)
+    "cvl_retina_atss_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "cvl_retina_atss_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, P, P, P,
+                                       c_size_t, P]),
+    "cvl_retina_atss_loss_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "cvl_retina_atss_loss": (c_int, [P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float,
+                                     c_float, P, P, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
     # Generalized Focal Loss (csrc/fcos_gfl.hip)
     "cvl_fcos_gfl_norm_workspace_size": (c_size_t, [c_int, c_int]),
     "cvl_fcos_gfl_norm": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
@@ -270,7 +277,8 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_conv_igemm_res_relu_plan", "cvl_pack_conv_weights_scaled_multi", "cvl_relu_", "cvl_eval_match_areas",
          "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign", "cvl_gconv3x3_plan",
          "cvl_fcos_gfl_norm_workspace_size", "cvl_fcos_gfl_norm", "cvl_fcos_gfl_loss_workspace_size",
-         "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode"}
+         "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode", "cvl_retina_atss_workspace_size", "cvl_retina_atss_assign",
+         "cvl_retina_atss_loss_workspace_size", "cvl_retina_atss_loss"}
 
 
 def load():

@@ -332,6 +332,73 @@ def retina_assign(boxes, nbox, img_dim, pad, anchor_dims, num_classes, iou_thres
     return out, nt
 
 
+# ---- ATSS for RetinaNet (cvlite extension; include/cvlite.h states the rules) ----------------------
+def retina_atss_assign(boxes, nbox, img_dim, pad, anchor_dims, num_classes, strides=RETINA_STRIDES, topk=9,
+                       out=None, num_targets=None, return_candidates=False):
+    """Batched ATSS targets for RetinaNet (cvl_retina_atss_assign): per box the topk anchors nearest its
+    centre on every level (the ceil(topk / A) nearest cells), positives where the anchor IoU reaches
+    mean + std of the box's own candidates and the anchor centre lies inside the box; per anchor the
+    largest IoU wins.  Inputs as retina_assign (anchor_dims: device fp32 [5, A, 2]).  Returns compact
+    targets [B, P, A, 8] f32 in the row order of the head outputs (slots: the four linear box targets,
+    label or -1, IoU, box index or -1, 0) and num_targets [B, 5] i32 = positive anchors per level; `out`
+    may be any contiguous f32 buffer of B*P*A*8 elements (e.g. [B, P*A, 8]).  return_candidates: also
+    (cand_idx [B,n_max,5*topk] i32 = target rows, cand_iou the same shape f32, cand_thr [B,n_max] f64)."""
+    B, nmax = _boxes_args(boxes, nbox, img_dim)
+    _lib.require_cuda(anchor_dims)
+    assert anchor_dims.dtype == torch.float32 and anchor_dims.dim() == 3 and tuple(anchor_dims.shape[::2]) == (5, 2)
+    A = int(anchor_dims.shape[1])
+    P = sum((int(pad) // int(s)) ** 2 for s in strides)
+    dev = boxes.device
+    if out is None:
+        out = torch.empty((B, P, A, 8), device=dev, dtype=torch.float32)
+    if num_targets is None:
+        num_targets = torch.empty((B, 5), device=dev, dtype=torch.int32)
+    assert out.numel() == B * P * A * 8 and out.dtype == torch.float32 and out.is_contiguous()
+    assert tuple(num_targets.shape) == (B, 5) and num_targets.dtype == torch.int32 and num_targets.is_contiguous()
+    cand = (None, None, None)
+    if return_candidates:
+        slots = 5 * max(int(topk), 0)
+        cand = (torch.empty((B, nmax, slots), device=dev, dtype=torch.int32),
+                torch.empty((B, nmax, slots), device=dev, dtype=torch.float32),
+                torch.empty((B, nmax), device=dev, dtype=torch.float64))
+    ws = torch.empty(int(_lib.load().cvl_retina_atss_workspace_size(B, P, A)), device=dev, dtype=torch.uint8)
+    st = (_lib.ctypes.c_int32 * 5)(*[int(s) for s in strides])
+    _lib.call("cvl_retina_atss_assign", ptr(boxes), ptr(nbox), ptr(img_dim), B, nmax, int(pad), int(num_classes),
+              ptr(anchor_dims), A, _lib.ctypes.cast(st, _lib.c_void_p), int(topk), ptr(out), ptr(num_targets),
+              ptr(cand[0]), ptr(cand[1]), ptr(cand[2]), ptr(ws), ws.numel(), _lib.stream())
+    return (out, num_targets) + cand if return_candidates else (out, num_targets)
+
+
+def retina_atss_loss(reg, cls, targets, num_targets, A, C, img_weight=None, alpha=0.25, gamma=2.0,
+                     grad_scale=1.0, d_reg=None, d_cls=None, losses=None):
+    """Focal + smooth-L1 on the compact ATSS targets, forward and backward (cvl_retina_atss_loss), each
+    image's sums divided by its positive anchors N = max(sum(num_targets[b]), 1).  reg [B,P,ld>=4A] /
+    cls [B,P,ld>=A*C] f32 from the grouped heads, targets B*P*A*8 f32 and num_targets [B,5] i32 from
+    retina_atss_assign, img_weight [B] f32 or None.  d_reg / d_cls: bf16 or fp32 buffers written at the
+    prediction positions (None = no gradient; padding channels are not touched).  Returns losses [B,2] =
+    (cls, reg)."""
+    _lib.require_cuda(reg, cls, targets, num_targets, img_weight, d_reg, d_cls)
+    B, P = int(reg.shape[0]), int(reg.shape[1])
+    assert reg.dtype == torch.float32 and cls.dtype == torch.float32 and targets.dtype == torch.float32
+    assert cls.shape[:2] == (B, P) and targets.numel() == B * P * int(A) * 8
+    assert tuple(num_targets.shape) == (B, 5) and num_targets.dtype == torch.int32
+    assert img_weight is None or (tuple(img_weight.shape) == (B,) and img_weight.dtype == torch.float32)
+    dev = targets.device
+    if losses is None:
+        losses = torch.empty((B, 2), device=dev, dtype=torch.float32)
+    assert losses.shape == (B, 2) and losses.dtype == torch.float32 and losses.is_contiguous()
+    for d in (d_reg, d_cls):
+        assert d is None or (d.shape[:2] == (B, P) and d.dtype in (torch.float32, torch.bfloat16))
+    ws = torch.empty(int(_lib.load().cvl_retina_atss_loss_workspace_size(B, P, int(A))), device=dev,
+                     dtype=torch.uint8)
+    dt = lambda t: 0 if t is None or t.dtype == torch.float32 else 1  # noqa: E731
+    _lib.call("cvl_retina_atss_loss", ptr(reg), int(reg.shape[2]), ptr(cls), int(cls.shape[2]), ptr(targets),
+              ptr(num_targets), ptr(img_weight), B, P, int(A), int(C), float(grad_scale), float(alpha), float(gamma),
+              ptr(losses), ptr(d_reg), int(d_reg.shape[2]) if d_reg is not None else 0, dt(d_reg), ptr(d_cls),
+              int(d_cls.shape[2]) if d_cls is not None else 0, dt(d_cls), ptr(ws), ws.numel(), _lib.stream())
+    return losses
+
+
 def centernet_assign(boxes, nbox, img_dim, pad_hw, num_classes, stride=8, out=None):
     """CenterNet hourglass centroid targets -> [B, pad_w/s, pad_h/s, 4+C]."""
     B, nmax = _boxes_args(boxes, nbox, img_dim)

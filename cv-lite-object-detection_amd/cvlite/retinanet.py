@@ -108,6 +108,13 @@ class RetinaNet(object):
         return ot.retina_assign(boxes, nbox, img_dim, pad, self.anchor_dims_device(), self.n_class,
                                 iou_thresh=iou_thresh, strides=self.strides, out=out, num_targets=num_targets)
 
+    def format_data_atss(self, boxes, nbox, img_dim, pad, topk=9, out=None, num_targets=None):
+        """ATSS targets (cvlite extension, cvl_retina_atss_assign): the inputs of format_data_batched ->
+        compact targets [B, P, A, 8] in the row order of the head outputs, positive anchors per level
+        [B, 5]; ops_targets.retina_atss_loss trains on them."""
+        return ot.retina_atss_assign(boxes, nbox, img_dim, pad, self.anchor_dims_device(), self.n_class,
+                                     strides=self.strides, topk=topk, out=out, num_targets=num_targets)
+
     def format_data(self, gt_labels, img_dim, iou_thresh=0.50, img_pad=None):
         """retinanet_module.py:251-365 -> (nested [5][A] float32 [S,S,4+C] maps, num_targets)."""
         if img_pad is None:

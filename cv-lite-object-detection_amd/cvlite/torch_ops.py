@@ -29,6 +29,11 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           head (cvlite extension): [B, 3] = (qfl, box,
                                                           dfl) with autograd as fcos_loss, and the
                                                           expected distances for inference
+  torch.ops.cvlite.retina_atss_assign(boxes, nbox, img_dim, pad, anchor_dims, C, topk),
+  torch.ops.cvlite.retina_atss_loss(reg, cls, targets, num_targets, img_weight, A, C)
+                                                          ATSS for RetinaNet (cvlite extension): compact
+                                                          targets [B, P, A, 8] and [B, 2] = (cls, reg) per
+                                                          image / its positive anchors, with autograd
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -341,6 +346,64 @@ def _paper_loss_backward(ctx, g):
 
 
 fcos_paper_loss.register_autograd(_paper_loss_backward, setup_context=_paper_loss_setup)
+
+
+# ---- ATSS for RetinaNet (cvlite extension) ------------------------------------------------------------
+@torch.library.custom_op("cvlite::retina_atss_assign", mutates_args=(), device_types="cuda")
+def retina_atss_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Tensor, pad: int,
+                       anchor_dims: torch.Tensor, num_classes: int, topk: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ATSS targets for RetinaNet (the topk nearest anchors per level, IoU threshold mean + std per box,
+    largest IoU per anchor) -> (compact targets [B,P,A,8] fp32 in the head outputs' row order, positive
+    anchors per level [B,5] i32); the loss op is retina_atss_loss."""
+    return ot.retina_atss_assign(boxes.contiguous(), nbox.contiguous(), img_dim.contiguous(), pad,
+                                 anchor_dims.contiguous(), num_classes, topk=topk)
+
+
+@retina_atss_assign.register_fake
+def _(boxes, nbox, img_dim, pad, anchor_dims, num_classes, topk):
+    A = anchor_dims.shape[1]
+    P = sum((pad // s) ** 2 for s in ot.RETINA_STRIDES)
+    B = boxes.shape[0]
+    return boxes.new_empty((B, P, A, 8)), nbox.new_empty((B, 5))
+
+
+@torch.library.custom_op("cvlite::retina_atss_loss", mutates_args=(), device_types="cuda")
+def retina_atss_loss(reg: torch.Tensor, cls: torch.Tensor, targets: torch.Tensor, num_targets: torch.Tensor,
+                     img_weight: Optional[torch.Tensor], n_anchors: int, num_classes: int, alpha: float = 0.25,
+                     gamma: float = 2.0) -> torch.Tensor:
+    """Normalised RetinaNet loss per image: reg [B,P,>=4A] fp32, cls [B,P,>=A*C] fp32, targets [B,P,A,8]
+    and num_targets [B,5] from retina_atss_assign, img_weight [B] or None -> [B,2] = (cls, reg)."""
+    return ot.retina_atss_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), num_targets.contiguous(),
+                               n_anchors, num_classes, img_weight=None if img_weight is None else img_weight.contiguous(),
+                               alpha=alpha, gamma=gamma)
+
+
+@retina_atss_loss.register_fake
+def _(reg, cls, targets, num_targets, img_weight, n_anchors, num_classes, alpha=0.25, gamma=2.0):
+    return reg.new_empty((reg.shape[0], 2))
+
+
+def _retina_atss_loss_setup(ctx, inputs, output):
+    reg, cls, targets, num_targets, img_weight, A, C, alpha, gamma = inputs
+    ctx.save_for_backward(reg, cls, targets, num_targets, img_weight)
+    ctx.args = (A, C, alpha, gamma)
+
+
+def _retina_atss_loss_backward(ctx, g):
+    reg, cls, targets, num_targets, img_weight = ctx.saved_tensors
+    A, C, alpha, gamma = ctx.args
+    # the kernel writes only the anchors' channels: the padding channels stay exactly zero
+    d_reg = torch.zeros_like(reg, memory_format=torch.contiguous_format)
+    d_cls = torch.zeros_like(cls, memory_format=torch.contiguous_format)
+    ot.retina_atss_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), num_targets.contiguous(), A, C,
+                        img_weight=None if img_weight is None else img_weight.contiguous(), alpha=alpha, gamma=gamma,
+                        grad_scale=1.0, d_reg=d_reg, d_cls=d_cls)
+    g = g.to(torch.float32)
+    # cls term -> class logits, reg term -> box outputs
+    return d_reg * g[:, 1].view(-1, 1, 1), d_cls * g[:, 0].view(-1, 1, 1), None, None, None, None, None, None, None
+
+
+retina_atss_loss.register_autograd(_retina_atss_loss_backward, setup_context=_retina_atss_loss_setup)
 
 
 # ---- Generalized Focal Loss (cvlite extension) --------------------------------------------------------

@@ -7,6 +7,10 @@
   the first batch_size candidates with matches (empty slots weight 0) and cvl_gather_rows moves
   their images / targets into the batch buffers -- no host round trip;
 * loss = cls + reg summed over the 45 (level, anchor) terms (cvl_retina_loss, fwd+bwd fused);
+* targets="atss" (cvlite extension): the candidates' targets come from cvl_retina_atss_assign instead
+  (compact rows [P*A][8] in the head outputs' order, positives chosen by each box's own IoU statistics),
+  a candidate is usable when it has a positive anchor, and the loss is cvl_retina_atss_loss, each image's
+  sums divided by its positive anchors; everything else in the step is the same;
 * gradients summed over the images, / batch_size (even when fewer were usable), clipped by
   global norm, Keras SGD momentum 0.9 (`tf.optimizers.SGD(momentum=0.9)`, :345);
 * lr = max(init_lr, min_lr) for step < 60000 and max(init_lr / 10, min_lr) for every step after
@@ -24,12 +28,17 @@ from . import ops_targets as ot
 from .retina_net import RetinaNetNet
 
 BF16 = torch.bfloat16
+TARGET_KINDS = ("reference", "atss")
 
 
 class RetinaTrainer(GraphStepper):
     def __init__(self, net, anchors, batch_size, img_size, n_max=64, init_lr=0.01, min_lr=1e-5,
-                 momentum=0.9, gradient_clip=1.0, candidates=3, world=1, use_graph=True, st_step=0):
+                 momentum=0.9, gradient_clip=1.0, candidates=3, world=1, use_graph=True, st_step=0,
+                 targets="reference", atss_topk=9):
         assert isinstance(net, RetinaNetNet)
+        if targets not in TARGET_KINDS:
+            raise ValueError("targets must be 'reference' or 'atss', not %r" % (targets,))
+        self.target_kind, self.atss_topk = targets, int(atss_topk)
         self.net, self.anchors = net, anchors
         self.B, self.S = batch_size, img_size
         self.nc = candidates * batch_size
@@ -43,16 +52,22 @@ class RetinaTrainer(GraphStepper):
         shapes, off, self.P = net.layout(B, S, S)
         self.level_cells = [h * w for h, w in shapes]
         T = self.A * self.P
+        # target rows per image: one-hot [A*P][4+C] in (level, anchor, cell) order, or ATSS's compact
+        # [P*A][8] in (cell, anchor) order (32-byte rows: cvl_gather_rows' 16-byte rule holds at every P)
+        row = 8 if targets == "atss" else 4 + self.C
         self.cand_images = torch.zeros((self.nc, S, S, 3), dtype=torch.float32, device=dev)
         self.cand_boxes = torch.zeros((self.nc, n_max, 5), dtype=torch.float32, device=dev)
         self.cand_nbox = torch.zeros((self.nc,), dtype=torch.int32, device=dev)
         self.cand_dim = torch.tensor([[float(S), float(S)]] * self.nc, dtype=torch.float32, device=dev)
-        self.cand_targets = torch.zeros((self.nc, T, 4 + self.C), dtype=torch.float32, device=dev)
+        self.cand_targets = torch.zeros((self.nc, T, row), dtype=torch.float32, device=dev)
         self.cand_counts = torch.zeros((self.nc,), dtype=torch.int32, device=dev)
         self.sel = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.img_w = torch.zeros((B,), dtype=torch.float32, device=dev)
         self.images = torch.zeros((B, S, S, 3), dtype=torch.float32, device=dev)
-        self.targets = torch.zeros((B, T, 4 + self.C), dtype=torch.float32, device=dev)
+        self.targets = torch.zeros((B, T, row), dtype=torch.float32, device=dev)
+        if targets == "atss":      # positive anchors per level, of the candidates and of the chosen images
+            self.cand_ntgt = torch.zeros((self.nc, 5), dtype=torch.int32, device=dev)
+            self.ntgt = torch.zeros((B, 5), dtype=torch.int32, device=dev)
         # padding channels of the head gradients must stay zero: written once, never touched
         self.d_reg = torch.zeros((B, self.P, net.reg_ld), dtype=net.store.act, device=dev)   # bf16 | fp32 parity
         self.d_cls = torch.zeros((B, self.P, net.cls_ld), dtype=net.store.act, device=dev)
@@ -63,15 +78,29 @@ class RetinaTrainer(GraphStepper):
         self._init_stepper(net, world, use_graph)
 
     def _fwd_bwd(self, hook=None):
-        self.anchors.format_data_batched(self.cand_boxes, self.cand_nbox, self.cand_dim, self.S,
-                                         out=self.cand_targets, num_targets=self.cand_counts)
+        atss = self.target_kind == "atss"
+        if atss:
+            self.anchors.format_data_atss(self.cand_boxes, self.cand_nbox, self.cand_dim, self.S,
+                                          topk=self.atss_topk, out=self.cand_targets, num_targets=self.cand_ntgt)
+            # 5 ints per candidate: the row sum and the pick below are index plumbing on 20-byte rows
+            # (cvl_gather_rows moves 16-byte multiples)
+            torch.sum(self.cand_ntgt, dim=1, dtype=torch.int32, out=self.cand_counts)
+        else:
+            self.anchors.format_data_batched(self.cand_boxes, self.cand_nbox, self.cand_dim, self.S,
+                                             out=self.cand_targets, num_targets=self.cand_counts)
         nn.select_first_nonzero(self.cand_counts, self.B, self.sel, self.img_w)
         nn.gather_rows(self.cand_images, self.sel, self.images)
         nn.gather_rows(self.cand_targets, self.sel, self.targets)
+        if atss:
+            torch.index_select(self.cand_ntgt, 0, self.sel, out=self.ntgt)
         reg, cls = self.net.forward(self.images)
         self.outputs = (reg, cls)
-        ot.retina_loss(reg, cls, self.targets, self.level_cells, self.A, self.C, img_weight=self.img_w,
-                       d_reg=self.d_reg, d_cls=self.d_cls, losses=self.losses)
+        if atss:
+            ot.retina_atss_loss(reg, cls, self.targets, self.ntgt, self.A, self.C, img_weight=self.img_w,
+                                d_reg=self.d_reg, d_cls=self.d_cls, losses=self.losses)
+        else:
+            ot.retina_loss(reg, cls, self.targets, self.level_cells, self.A, self.C, img_weight=self.img_w,
+                           d_reg=self.d_reg, d_cls=self.d_cls, losses=self.losses)
         self.net.backward(self.d_reg, self.d_cls, hook=hook)
 
     def _update(self):
@@ -122,8 +151,10 @@ def synthetic_coco_batch(n, S, n_classes=80, n_max=50, seed=1234, device="cuda")
 # -------------------------------------------------------------------------------------------------
 def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_manager, st_step, max_steps,
           init_lr=1e-3, min_lr=1e-5, decay_step=1000, decay_rate=0.99, img_dims=512, display_step=50,
-          step_save=100, step_cool=1000, gradient_clip=1.0, save_loss_file="train_losses.csv"):
-    """Same keywords as train_retinanet_coco.py:145-150.  `model` is a cvlite.retinanet.RetinaNet;
+          step_save=100, step_cool=1000, gradient_clip=1.0, save_loss_file="train_losses.csv", recipe="reference",
+          atss_topk=9):
+    """Same keywords as train_retinanet_coco.py:145-150, plus recipe / atss_topk (cvlite extension:
+    recipe="atss" trains with RetinaTrainer(targets="atss", atss_topk), "reference" is the default).  `model` is a cvlite.retinanet.RetinaNet;
     `train_data` a list of pre-processed samples dict(image=[S,S,3] in [-1,1], bbox=[N,4] normalised
     (yc,xc,h,w), label=[N]) of one square size S (decode/resize are outside this tier).  Per step
     3*batch_size candidates are drawn without replacement; the device picks the first batch_size
@@ -133,11 +164,14 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
     import os
     import time
     from . import checkpoint as ck
+    if recipe not in TARGET_KINDS:
+        raise ValueError("recipe must be 'reference' or 'atss', not %r" % (recipe,))
     n_data = len(train_data)
     S = int(train_data[0]["image"].shape[0])
     n_max = max(16, max(len(s["label"]) for s in train_data))
     trainer = RetinaTrainer(model.model, model, batch_size, S, n_max=n_max, init_lr=init_lr, min_lr=min_lr,
-                            momentum=optimizer.momentum, gradient_clip=gradient_clip, st_step=st_step)
+                            momentum=optimizer.momentum, gradient_clip=gradient_clip, st_step=st_step,
+                            targets=recipe, atss_topk=atss_topk)
     dev = model.model.device
     start = time.time()
     batch_objs = total_loss = trend_loss = 0.0

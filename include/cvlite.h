@@ -207,6 +207,75 @@ int cvl_fcos_atss_assign(const float* boxes, const int32_t* nbox, const float* i
                          cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ATSS target assignment and a per-image normalised loss for RetinaNet (the same paper: ATSS was
+ * published to bridge RetinaNet and FCOS): an extension beyond the reference.  The targets are compact,
+ * 8 floats per anchor in the row order of the head outputs, instead of cvl_retina_assign's one-hot rows.
+ *
+ * cvl_retina_atss_assign: inputs of cvl_retina_assign (boxes [B][n_max][5] = (yc, xc, h, w, label)
+ * normalised, nbox [B], img_dim [B][2], a square pad, anchor_dims DEVICE [5][A][2] = (h, w), strides HOST
+ * [5]) plus topk.  targets [B][P][A][8], 16-byte aligned: cell-major over the level-major cells (level l
+ * has S = pad/stride_l cells a side, cell = u*S + v, P = sum_l S*S), anchor-minor.  num_targets [B][5] =
+ * POSITIVE ANCHORS per level.  Limits: n_max <= 256, 1 <= A <= 16, 1 <= topk <= 144 and
+ * ceil(topk/A) <= 16, pad a positive multiple of 128 and of every stride, 1 <= C <= 256; anything else
+ * returns the invalid-argument status and writes nothing.  fp32 in this operation order (no
+ * contraction) except where float64 is named:
+ *   box i < clamp(nbox[b], 0, n_max): yc, xc, hp, wp, y0, y1, x0, x1, area and the validity test exactly
+ *     as in cvl_fcos_atss_assign (skipped unless -1 < label < C and area > 0)
+ *   anchor positions as cvl_retina_assign / cvl_retina_decode: the A anchors of cell (u, v) of level l
+ *     are centred at c0 = (float)(u*s) in y, c1 = (float)(v*s) in x (no +0.5), with dims
+ *     (ah, aw) = anchor_dims[l][an]
+ *   1 candidates, per level: dy = c0 - yc, dx = c1 - xc, d2 = dy*dy + dx*dx (ordered by its bit pattern,
+ *     a NaN above +inf); the candidates are the k_l = min(topk, A*S*S) anchors with the smallest d2, ties
+ *     to the lowest cell*A + an, ranked in that order.  All A anchors of a cell tie, so these are the
+ *     ceil(k_l/A) nearest cells, each in full except possibly the last: rank j is anchor j % A of the
+ *     cell of rank j / A
+ *   2 IoU of a candidate: ih = fmaxf(fminf(y1, c0+ah*0.5f) - fmaxf(y0, c0-ah*0.5f), 0), iw likewise in x
+ *     with aw; inter = ih*iw; uni = (ah*aw + area) - inter; iou = (float)((double)inter / (double)uni)
+ *   3 threshold, float64, over the n = sum_l k_l candidates level-major and then by rank: mean + sample
+ *     standard deviation, exactly as step 3 of cvl_fcos_atss_assign
+ *   4 positive pair (box, anchor): the anchor is a candidate of the box, (double)iou >= thr, and each of
+ *     c0 - y0, y1 - c0, c1 - x0, x1 - c1 is > 0.01f
+ *   per anchor: among its positive pairs the largest iou wins, ties to the lowest box index (a 64-bit
+ *     integer max of iou bits << 32 | ~box).  The row of a positive anchor: slots 0..3 the linear box
+ *     targets of cvl_retina_assign in float64 rounded to fp32, (c0 - yc)/ah, (c1 - xc)/aw, hp/ah, wp/aw;
+ *     slot 4 (float)label; slot 5 the winning iou; slot 6 (float)box index; slot 7 zero.  The row of any
+ *     other anchor is 0, 0, 0, 0, -1, 0, -1, 0.
+ * Optional outputs (null: not written): cand_idx int32 [B][n_max][5*topk] = the target row
+ * (off_l + cell)*A + an in [0, P*A) by level and rank, or -1; cand_iou float, the same shape, 0 where
+ * cand_idx is -1; cand_thr double [B][n_max]; boxes that are skipped or past nbox get -1 / 0 / 0.
+ * workspace >= cvl_retina_atss_workspace_size(B, P, A) bytes, 8-byte aligned (one 64-bit contest key per
+ * anchor).  Graph-safe: no host synchronisation, no allocation; its clears are memset nodes.
+ * Bit-identical from run to run.
+ *
+ * cvl_retina_atss_loss: fused forward + backward on those targets.  reg_pred [B][P][ld_reg >= 4A] with
+ * anchor a at channels 4a..4a+3, cls_pred [B][P][ld_cls >= A*C] with anchor a at channels aC..aC+C-1
+ * (the grouped heads' rows); targets / num_targets as the assign call writes them; img_weight [B] or null
+ * (= 1).  Per element, fp32: class = the focal term of cvl_fcos_paper_loss with y = 1 iff the anchor's
+ * label (slot 4) equals the class; box = the smooth-L1 element of cvl_retina_loss between slots 0..3 and
+ * the four box outputs, on the positive anchors only (label >= 0; the box slots of the others are never
+ * read).  Per image, N_b = max(sum_l num_targets[b][l], 1), wb = img_weight[b]:
+ *   losses[b] = (cls, reg) = (float)(wb * sum / (double)N_b), the sums as float64 per-tile partials and
+ *     a fixed-order second pass (no float atomics: bit-identical from run to run)
+ *   a gradient element is g * gs with gs = (grad_scale * wb) / (float)N_b; the box gradient of a
+ *     non-positive anchor is written as 0; channels at or beyond 4A / A*C are not touched.
+ * d_reg / d_cls: fp32 (dtype 0) or bf16 (1) with leading dimensions of their own, or null for forward
+ * only.  workspace >= cvl_retina_atss_loss_workspace_size(B, P, A) bytes, 8-byte aligned; targets 16-byte
+ * aligned.  Arguments out of range return the invalid-argument status and write nothing.  Graph-safe.
+ * ---------------------------------------------------------------------------------------- */
+size_t cvl_retina_atss_workspace_size(int B, int P, int n_anchors);
+int cvl_retina_atss_assign(const float* boxes, const int32_t* nbox, const float* img_dim, int B, int n_max, int pad,
+                           int num_classes, const float* anchor_dims, int n_anchors,
+                           const int32_t* strides /*host[5]*/, int topk, float* targets, int32_t* num_targets,
+                           int32_t* cand_idx, float* cand_iou, double* cand_thr, void* workspace,
+                           size_t workspace_bytes, cvl_stream_t stream);
+size_t cvl_retina_atss_loss_workspace_size(int B, int P, int n_anchors);
+int cvl_retina_atss_loss(const float* reg_pred, int ld_reg, const float* cls_pred, int ld_cls, const float* targets,
+                         const int32_t* num_targets, const float* img_weight, int B, int P, int n_anchors,
+                         int num_classes, float grad_scale, float alpha, float gamma, float* losses, void* d_reg,
+                         int ld_dreg, int dreg_dtype, void* d_cls, int ld_dcls, int dcls_dtype, void* workspace,
+                         size_t workspace_bytes, cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generalized Focal Loss for the FCOS head (Li et al., NeurIPS 2020, "Generalized Focal Loss: Learning
  * Qualified and Distributed Bounding Boxes for Dense Object Detection"): an extension beyond the
  * reference, trained on the targets of cvl_fcos_atss_assign (or cvl_fcos_paper_assign).  The
