@@ -62,6 +62,12 @@ SIGNATURES = {
     "cvl_fcos_gfl_loss": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
                                   c_float, P, P, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
     "cvl_fcos_gfl_decode": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
+    # CenterNet Gaussian targets and penalty-reduced focal loss (csrc/centernet_gauss.hip)
+    "cvl_centernet_gauss_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
+    "cvl_centernet_gauss_norm": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "cvl_centernet_gauss_loss_workspace_size": (c_size_t, [c_int, c_int]),
+    "cvl_centernet_gauss_loss": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                         P, P, c_int, P, P]),
     "cvl_fcos_decode": (c_int, [P, c_int, c_int, c_int, ctypes.c_double, P, P]),
     "cvl_fcos_v1_decode": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P]),
     "cvl_conv_igemm_workspace_size": (c_size_t, [P]),
@@ -278,7 +284,8 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_eval_ap_views", "cvl_fcos_atss_workspace_size", "cvl_fcos_atss_assign", "cvl_gconv3x3_plan",
          "cvl_fcos_gfl_norm_workspace_size", "cvl_fcos_gfl_norm", "cvl_fcos_gfl_loss_workspace_size",
          "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode", "cvl_retina_atss_workspace_size", "cvl_retina_atss_assign",
-         "cvl_retina_atss_loss_workspace_size", "cvl_retina_atss_loss"}
+         "cvl_retina_atss_loss_workspace_size", "cvl_retina_atss_loss", "cvl_centernet_gauss_assign",
+         "cvl_centernet_gauss_norm", "cvl_centernet_gauss_loss_workspace_size", "cvl_centernet_gauss_loss"}
 
 
 def load():

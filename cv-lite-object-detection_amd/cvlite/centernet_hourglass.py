@@ -1,7 +1,9 @@
 """Drop-in mirror of CenterNet/tf_centernet_hourglass.py on MI355X: `build_model` (the separable
 hourglass, cvlite.hourglass_net), `train_step` (cvlite.train_centernet: sub-batch BN, fused loss,
 clip + Adam, HIP graphs), `format_data` (cvl_centernet_assign), `model_loss` (cvl_det_loss), `nms`
-(cvl_nms), `prediction_to_corners` (cvl_fcos_decode: same formula, :355-377)."""
+(cvl_nms), `prediction_to_corners` (cvl_fcos_decode: same formula, :355-377).  Beyond the reference:
+`format_data_gaussian` and `train_step(recipe="gaussian")` (the *Objects as Points* recipe,
+cvl_centernet_gauss_*), `peak_detections` (cvl_centernet_peak_decode)."""
 import numpy as np
 import torch
 
@@ -22,6 +24,25 @@ def format_data(gt_labels, img_dim, num_classes, img_pad=None, stride=8):
     out = ot.centernet_assign(torch.tensor(boxes, device="cuda"), torch.tensor([n], dtype=torch.int32, device="cuda"),
                               torch.tensor(np.asarray(img_dim, np.float32).reshape(1, 2), device="cuda"),
                               (int(img_pad[0]), int(img_pad[1])), num_classes, stride=stride)
+    return out[0].cpu().numpy(), n
+
+
+def format_data_gaussian(gt_labels, img_dim, num_classes, img_pad=None, stride=8, min_overlap=0.7):
+    """One image's Gaussian-heatmap targets (a cvlite extension, cvl_centernet_gauss_assign): inputs as
+    format_data -> (float32 [pad_h/s, pad_w/s, 4+C], rows along y, num_targets).  The maps
+    train_step(..., recipe="gaussian") takes."""
+    if img_pad is None:
+        img_pad = [int(float(v)) for v in np.asarray(img_dim, np.float32)]
+    gt = np.asarray(gt_labels, dtype=np.float32).reshape(-1, 5)
+    n = len(gt)
+    boxes = np.zeros((1, max(n, 1), 5), np.float32)
+    boxes[0, :n] = gt
+    _lib.require_cuda()
+    out = ot.centernet_gauss_assign(torch.tensor(boxes, device="cuda"),
+                                    torch.tensor([n], dtype=torch.int32, device="cuda"),
+                                    torch.tensor(np.asarray(img_dim, np.float32).reshape(1, 2), device="cuda"),
+                                    (int(img_pad[0]), int(img_pad[1])), num_classes, stride=stride,
+                                    min_overlap=min_overlap)
     return out[0].cpu().numpy(), n
 
 
@@ -71,20 +92,25 @@ def build_model(n_classes, tmp_pi=0.99, n_filters=128, n_stacks=1, n_repeats=2, 
 
 
 def train_step(voc_model, sub_batch_sz, images, bboxes, optimizer, cls_lambda=2.5, reg_lambda=1.0,
-               learning_rate=1.0e-3, grad_clip=1.0):
+               learning_rate=1.0e-3, grad_clip=1.0, recipe="reference"):
     """tf_centernet_hourglass.py:507-564.  images [B,H,W,3] fp32, bboxes = formatted targets
     [B,H/4,W/4,4+C]; optimizer = cvlite.train_centernet.Adam (tf.keras.optimizers.Adam stand-in).
-    Returns (avg_cls_loss, avg_reg_loss) = per-batch sums / batch_size."""
+    Returns (avg_cls_loss, avg_reg_loss) = per-batch sums / batch_size.  recipe="gaussian" (a cvlite
+    extension): bboxes are format_data_gaussian's maps and the loss is the penalty-reduced focal loss +
+    L1 on the centres, per image divided by its number of objects (CenterNetTrainer targets="gaussian")."""
     from .train_centernet import CenterNetTrainer
+    if recipe not in ("reference", "gaussian"):
+        raise ValueError("recipe must be 'reference' or 'gaussian', got %r" % (recipe,))
     _lib.require_cuda()
     images = torch.as_tensor(images, dtype=torch.float32).cuda()
     bboxes = torch.as_tensor(bboxes, dtype=torch.float32).cuda()
     B, H, W, _ = images.shape
-    key = (B, H, W, int(sub_batch_sz), id(optimizer), float(cls_lambda), float(reg_lambda), float(grad_clip))
+    key = (B, H, W, int(sub_batch_sz), id(optimizer), float(cls_lambda), float(reg_lambda), float(grad_clip),
+           recipe)
     tr = getattr(voc_model, "_trainers", {}).get(key)
     if tr is None:
         tr = CenterNetTrainer(voc_model, B, (H, W), sub_batch_sz=sub_batch_sz, optimizer=optimizer,
-                              cls_lambda=cls_lambda, reg_lambda=reg_lambda, grad_clip=grad_clip)
+                              cls_lambda=cls_lambda, reg_lambda=reg_lambda, grad_clip=grad_clip, targets=recipe)
         voc_model._trainers = getattr(voc_model, "_trainers", {})
         voc_model._trainers[key] = tr
     tr.opt.lr_dev.fill_(float(learning_rate))                    # optimizer.lr.assign(learning_rate)

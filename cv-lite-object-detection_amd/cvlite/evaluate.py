@@ -552,19 +552,29 @@ def evaluate_retinanet(retina, samples, num_classes=None, batch_size=16, protoco
 
 
 def evaluate_centernet(model, samples, num_classes, batch_size=16, protocol="voc07", iou_thresholds=None,
-                       max_dets=100, area_ranges=None, shard=None, group=None, return_state=False, **decode_kwargs):
+                       max_dets=100, area_ranges=None, shard=None, group=None, return_state=False, decode="nms",
+                       K=100, **decode_kwargs):
     """The separable-hourglass CenterNet (cvlite.centernet_hourglass.build_model): inference forward
-    per batch, centernet_hourglass.decode_detections per image (threshold + NMS; rows (x1, y1, x2,
-    y2, score, class)), Evaluator.add_rows.  decode_kwargs: thresh, iou_thresh, downsample (default:
-    the model's stride) of decode_detections."""
-    from .centernet_hourglass import decode_detections
+    per batch, then Evaluator.add_rows on rows (x1, y1, x2, y2, score, class).  decode="nms" (default):
+    centernet_hourglass.decode_detections per image (the reference's threshold + NMS); decode_kwargs:
+    thresh, iou_thresh, downsample (default: the model's stride).  decode="peak": one batched
+    centernet_hourglass.peak_detections call per batch (3x3 max-pool peaks, the K best per image, no
+    per-image host synchronisation) -- the decode that heat maps trained with targets="gaussian" are
+    made for; decode_kwargs: thresh, downsample."""
+    from .centernet_hourglass import decode_detections, peak_detections
+    if decode not in ("nms", "peak"):
+        raise ValueError("decode must be 'nms' or 'peak', not %r" % (decode,))
     ev = Evaluator(num_classes, protocol, iou_thresholds=iou_thresholds, max_dets=max_dets, area_ranges=area_ranges)
     for imgs, gt, ids, real, extra in _sample_batches(samples, batch_size, shard, areas=area_ranges is not None):
         H, W = imgs.shape[1:3]
         pred = model(torch.from_numpy(imgs).cuda(), training=False)
         kw = dict(decode_kwargs)
         kw.setdefault("downsample", H // int(pred.shape[1]))
-        rows = [decode_detections(pred[b], img_rows=H, img_cols=W, **kw)[1][:MAX_T] for b in range(real)]
+        if decode == "peak":
+            dets = peak_detections(pred, K=int(K), num_classes=num_classes, **kw)
+            rows = [d[:MAX_T][:, [1, 0, 3, 2, 4, 5]] for d in dets[:real]]
+        else:
+            rows = [decode_detections(pred[b], img_rows=H, img_cols=W, **kw)[1][:MAX_T] for b in range(real)]
         ev.add_rows(rows, _gt_rows(gt, real, extra["gt_area"]), fmt="xyxy", image_ids=ids[:real],
                     area_scale=_row_scale(extra, real))
     return _finish(ev, group, return_state)

@@ -410,6 +410,62 @@ def centernet_assign(boxes, nbox, img_dim, pad_hw, num_classes, stride=8, out=No
     return out
 
 
+# ---- CenterNet Gaussian targets (cvlite extension; include/cvlite.h states the rules) -----------------
+def centernet_gauss_assign(boxes, nbox, img_dim, pad_hw, num_classes, stride=4, min_overlap=0.7, out=None):
+    """Gaussian-heatmap CenterNet targets (cvl_centernet_gauss_assign): per kept box a disc of radius
+    mmdet's gaussian_radius(min_overlap) about its centre cell, heat exp(-d^2 / (2 sigma^2)) with sigma =
+    (2r + 1) / 6, per class the maximum over the boxes, exactly 1.0 at the centres; the box channels are
+    centernet_assign's at the centre cells.  Inputs as centernet_assign.  Returns [B, pad_h/s, pad_w/s,
+    4+C] f32 (rows along y; centernet_assign's layout for square pads)."""
+    B, nmax = _boxes_args(boxes, nbox, img_dim)
+    hm, wm = int(pad_hw[0]) // int(stride), int(pad_hw[1]) // int(stride)
+    if out is None:
+        out = torch.empty((B, hm, wm, 4 + num_classes), device=boxes.device, dtype=torch.float32)
+    assert out.numel() == B * hm * wm * (4 + num_classes) and out.dtype == torch.float32 and out.is_contiguous()
+    _lib.call("cvl_centernet_gauss_assign", ptr(boxes), ptr(nbox), ptr(img_dim), B, nmax, int(pad_hw[0]),
+              int(pad_hw[1]), int(num_classes), int(stride), float(min_overlap), ptr(out), _lib.stream())
+    return out
+
+
+def centernet_gauss_norm(targets, num_classes, out=None):
+    """npos [B] i32 = the (cell, class) entries of each image's target map [B, ..., 4+C] that equal 1.0
+    (cvl_centernet_gauss_norm): the divisor N of centernet_gauss_loss, for assigned and loaded maps alike."""
+    _lib.require_cuda(targets, out)
+    assert targets.dtype == torch.float32 and targets.shape[-1] == 4 + num_classes
+    B = int(targets.shape[0])
+    P = int(targets.numel() // (B * (4 + num_classes)))
+    if out is None:
+        out = torch.empty((B,), device=targets.device, dtype=torch.int32)
+    assert tuple(out.shape) == (B,) and out.dtype == torch.int32
+    _lib.call("cvl_centernet_gauss_norm", ptr(targets), B, P, int(num_classes), ptr(out), _lib.stream())
+    return out
+
+
+def centernet_gauss_loss(pred, targets, npos, num_classes, alpha=2.0, beta=4.0, cls_scale=1.0, reg_scale=1.0,
+                         d_pred=None, losses=None):
+    """Penalty-reduced focal loss + L1 on the centres, forward and backward (cvl_centernet_gauss_loss), each
+    image's sums divided by N = max(npos[b], 1).  pred [B,P,ld] f32 (box 0..3, class logits 4..), targets
+    [B,P,4+C] f32, npos [B] i32 from centernet_gauss_norm.  Returns (losses [B,2] = (cls, reg), not scaled,
+    d_pred bf16 [B,P,ld_d] of cls_scale*cls + reg_scale*reg, channels >= 4+C zero)."""
+    _lib.require_cuda(pred, targets, npos, d_pred, losses)
+    B, P = int(targets.shape[0]), int(targets.shape[1])
+    assert pred.dtype == torch.float32 and targets.dtype == torch.float32 and npos.dtype == torch.int32
+    assert targets.shape[-1] == 4 + num_classes and pred.numel() == B * P * pred.shape[-1]
+    assert tuple(npos.shape) == (B,)
+    dev = targets.device
+    if losses is None:
+        losses = torch.empty((B, 2), device=dev, dtype=torch.float32)
+    if d_pred is None:
+        d_pred = torch.empty((B, P, (4 + num_classes + 7) // 8 * 8), device=dev, dtype=torch.bfloat16)
+    assert losses.shape == (B, 2) and losses.dtype == torch.float32
+    assert d_pred.dtype == torch.bfloat16 and d_pred.numel() == B * P * d_pred.shape[-1]
+    ws = torch.empty(int(_lib.load().cvl_centernet_gauss_loss_workspace_size(B, P)), device=dev, dtype=torch.uint8)
+    _lib.call("cvl_centernet_gauss_loss", ptr(pred), int(pred.shape[-1]), ptr(targets), ptr(npos), B, P,
+              int(num_classes), float(alpha), float(beta), float(cls_scale), float(reg_scale), ptr(losses),
+              ptr(d_pred), int(d_pred.shape[-1]), ptr(ws), _lib.stream())
+    return losses, d_pred
+
+
 def centernet_splat(boxes, nbox, img_dim, pad_hw, num_classes, stride=8, sigma=0.25):
     """CenterNet centre splat targets -> [B, pad_h/s, pad_w/s, 5+C]."""
     B, nmax = _boxes_args(boxes, nbox, img_dim)

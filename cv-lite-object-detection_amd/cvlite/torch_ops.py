@@ -34,6 +34,12 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           ATSS for RetinaNet (cvlite extension): compact
                                                           targets [B, P, A, 8] and [B, 2] = (cls, reg) per
                                                           image / its positive anchors, with autograd
+  torch.ops.cvlite.centernet_gauss_assign(boxes, nbox, img_dim, pad_h, pad_w, C, stride, min_overlap),
+  torch.ops.cvlite.centernet_gauss_loss(pred, targets, npos, C, alpha, beta)
+                                                          CenterNet as "Objects as Points" trains it (cvlite
+                                                          extension): Gaussian heat maps [B, H/s, W/s, 4+C] with
+                                                          their object counts [B], and [B, 2] = (cls, reg) per
+                                                          image / its objects, with autograd on pred
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -472,6 +478,70 @@ def fcos_gfl_decode(reg: torch.Tensor, reg_max: int) -> torch.Tensor:
 @fcos_gfl_decode.register_fake
 def _(reg, reg_max):
     return reg.new_empty(tuple(reg.shape[:-1]) + (8,))
+
+
+# ---- CenterNet Gaussian targets and penalty-reduced focal loss (cvlite extension) ---------------------
+@torch.library.custom_op("cvlite::centernet_gauss_assign", mutates_args=(), device_types="cuda")
+def centernet_gauss_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Tensor, pad_h: int, pad_w: int,
+                           num_classes: int, stride: int = 4,
+                           min_overlap: float = 0.7) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gaussian-heatmap CenterNet targets for a batch -> (targets [B, pad_h/s, pad_w/s, 4+C] fp32, npos [B]
+    i32 = the (cell, class) entries equal to 1.0, the divisor of centernet_gauss_loss)."""
+    t = ot.centernet_gauss_assign(boxes.contiguous(), nbox.contiguous(), img_dim.contiguous(), (pad_h, pad_w),
+                                  num_classes, stride=stride, min_overlap=min_overlap)
+    return t, ot.centernet_gauss_norm(t, num_classes)
+
+
+@centernet_gauss_assign.register_fake
+def _(boxes, nbox, img_dim, pad_h, pad_w, num_classes, stride=4, min_overlap=0.7):
+    B = boxes.shape[0]
+    return boxes.new_empty((B, pad_h // stride, pad_w // stride, 4 + num_classes)), nbox.new_empty((B,))
+
+
+def _gauss_rows(pred, targets, num_classes):
+    B = int(targets.shape[0])
+    return (pred.contiguous().view(B, -1, pred.shape[-1]),
+            targets.contiguous().view(B, -1, 4 + num_classes))
+
+
+@torch.library.custom_op("cvlite::centernet_gauss_loss", mutates_args=(), device_types="cuda")
+def centernet_gauss_loss(pred: torch.Tensor, targets: torch.Tensor, npos: torch.Tensor, num_classes: int,
+                         alpha: float = 2.0, beta: float = 4.0) -> torch.Tensor:
+    """Penalty-reduced focal loss + L1 on the centres per image: pred [B,...,>=4+C] fp32 (box 0..3, class
+    logits 4..), targets [B,...,4+C], npos [B] i32 -> [B,2] = (cls, reg), each divided by max(npos, 1)."""
+    p, t = _gauss_rows(pred, targets, num_classes)
+    losses, _ = ot.centernet_gauss_loss(p, t, npos.contiguous(), num_classes, alpha=alpha, beta=beta)
+    return losses
+
+
+@centernet_gauss_loss.register_fake
+def _(pred, targets, npos, num_classes, alpha=2.0, beta=4.0):
+    return pred.new_empty((pred.shape[0], 2))
+
+
+def _gauss_loss_setup(ctx, inputs, output):
+    pred, targets, npos, C, alpha, beta = inputs
+    ctx.save_for_backward(pred, targets, npos)
+    ctx.args = (C, alpha, beta)
+
+
+def _gauss_loss_backward(ctx, g):
+    pred, targets, npos = ctx.saved_tensors
+    C, alpha, beta = ctx.args
+    p, t = _gauss_rows(pred, targets, C)
+    ld = int(p.shape[-1])
+    d = torch.empty((p.shape[0], p.shape[1], (ld + 7) // 8 * 8), dtype=BF16, device=p.device)
+    ot.centernet_gauss_loss(p, t, npos.contiguous(), C, alpha=alpha, beta=beta, d_pred=d)
+    g = g.to(torch.float32)
+    # the kernel's gradient is bf16 (the output conv's backward operand); cls term -> class logits, reg
+    # term -> box channels 0..3, padding channels exactly zero
+    scale = torch.zeros((p.shape[0], 1, ld), dtype=torch.float32, device=p.device)
+    scale[:, 0, :4] = g[:, 1:2]
+    scale[:, 0, 4:4 + C] = g[:, 0:1]
+    return (d[..., :ld].to(torch.float32) * scale).view(pred.shape), None, None, None, None, None
+
+
+centernet_gauss_loss.register_autograd(_gauss_loss_backward, setup_context=_gauss_loss_setup)
 
 
 # ---- optimizer -----------------------------------------------------------------------------------

@@ -8,6 +8,13 @@ sub-batch of `sub_batch_sz` images (one Keras training forward per sub-batch), t
 model_loss forward + backward (2.5 cls + 1.0 reg), backward, (RCCL gradient all-reduce),
 divide_no_nan(g, batch_size), clip_by_global_norm, Keras Adam, then the separable-conv fold and
 bf16 re-pack — captured into two HIP graphs (fwd+bwd, update) and replayed.
+
+`targets="gaussian"` (a cvlite extension; the default "reference" is the recipe above, unchanged) trains
+as "Objects as Points" does: Gaussian heat about every centre (cvl_centernet_gauss_assign, radius from
+`min_overlap`), the penalty-reduced focal loss with `focal_alpha` / `focal_beta` and L1 on the centres'
+box channels, each image's sums divided by its number of objects N (cvl_centernet_gauss_norm; on loaded
+maps too).  The lambdas keep their meaning and defaults (2.5 / 1.0; the paper trains with 1.0 / 0.1).  N
+is per image, so the gradient divisor stays 1 / (batch_size * world) and data parallel needs nothing new.
 """
 import numpy as np
 import torch
@@ -59,7 +66,12 @@ class Adam(object):
 
 class CenterNetTrainer(GraphStepper):
     def __init__(self, net, batch_size, image_hw, sub_batch_sz=2, n_max=64, optimizer=None, cls_lambda=2.5,
-                 reg_lambda=1.0, grad_clip=1.0, world=1, use_graph=True):
+                 reg_lambda=1.0, grad_clip=1.0, world=1, use_graph=True, targets="reference", min_overlap=0.7,
+                 focal_alpha=2.0, focal_beta=4.0):
+        if targets not in ("reference", "gaussian"):
+            raise ValueError("targets must be 'reference' or 'gaussian', got %r" % (targets,))
+        self.recipe = targets
+        self.min_overlap, self.focal_alpha, self.focal_beta = float(min_overlap), float(focal_alpha), float(focal_beta)
         self.net = net
         self.B = batch_size
         self.H, self.W = image_hw
@@ -80,10 +92,14 @@ class CenterNetTrainer(GraphStepper):
         self.targets = torch.zeros((B, self.Ho, self.Wo, 4 + self.C), dtype=torch.float32, device=dev)
         self.d_out = torch.zeros((B, self.Ho, self.Wo, net.cout_ld), dtype=torch.bfloat16, device=dev)
         self.losses = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        if self.recipe == "gaussian":                 # objects per image, the loss's divisor
+            self.npos = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.assign = True
         self._init_stepper(net, world, use_graph)
 
     def _fwd_bwd(self, hook=None):
+        if self.recipe == "gaussian":
+            return self._fwd_bwd_gaussian(hook)
         if self.assign:
             ot.centernet_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C, stride=self.stride,
                                 out=self.targets)
@@ -91,6 +107,19 @@ class CenterNetTrainer(GraphStepper):
         ot.centernet_loss(out.view(self.B, self.P, -1), self.targets.view(self.B, self.P, -1), self.C,
                           self.cls_lambda, self.reg_lambda, d_pred=self.d_out.view(self.B, self.P, -1),
                           losses=self.losses)
+        self.out = out
+        self.net.backward(self.d_out, hook=hook)
+
+    def _fwd_bwd_gaussian(self, hook=None):
+        if self.assign:
+            ot.centernet_gauss_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
+                                      stride=self.stride, min_overlap=self.min_overlap, out=self.targets)
+        ot.centernet_gauss_norm(self.targets, self.C, out=self.npos)
+        out = self.net.forward(self.images, group=self.group)
+        ot.centernet_gauss_loss(out.view(self.B, self.P, -1), self.targets.view(self.B, self.P, -1), self.npos,
+                                self.C, alpha=self.focal_alpha, beta=self.focal_beta, cls_scale=self.cls_lambda,
+                                reg_scale=self.reg_lambda, d_pred=self.d_out.view(self.B, self.P, -1),
+                                losses=self.losses)
         self.out = out
         self.net.backward(self.d_out, hook=hook)
 

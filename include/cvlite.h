@@ -332,6 +332,66 @@ int cvl_fcos_gfl_decode(const float* reg_pred, int ld_reg, int rows, int reg_max
                         cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CenterNet as the paper trains it (Zhou et al., 2019, "Objects as Points"): an extension beyond the
+ * reference.  Gaussian heat about every object centre, the penalty-reduced focal loss, L1 on the box
+ * channels of the centres, every sum divided by the image's number of objects.  The reference's recipe
+ * (cvl_centernet_assign / cvl_centernet_loss: one-hot centres, full-weight negatives, plain sums) is
+ * unchanged.  The model output keeps the reference's ltrb box channels (no size / offset heads), so
+ * cvl_centernet_decode and cvl_centernet_peak_decode read it as before.  Compiled without contraction;
+ * fp32 unless float64 is named.
+ *
+ * cvl_centernet_gauss_assign: boxes [B][n_max][5] = (yc, xc, h, w, label) normalised, nbox [B], img_dim
+ * [B][2] = (H, W), n_max <= 256, num_classes = C <= 256, 0 < min_overlap < 1 -> targets
+ * [B][hm = pad_h/stride][wm = pad_w/stride][4+C], rows along y.  (cvl_centernet_assign keeps the
+ * reference's swap of the two pads; the two layouts and paddings coincide when pad_h == pad_w and
+ * H == W.)  Per box, in fp32 with s = (float)stride, the expressions of cvl_centernet_assign:
+ *   c0 = (yc - 0.5f h) H, c1 = (xc - 0.5f w) W, c2 = (yc + 0.5f h) H, c3 = (xc + 0.5f w) W;
+ *   pad_y = (float)(int)((pad_h - H) / 2.0f), pad_x = (float)(int)((pad_w - W) / 2.0f);
+ *   ycf = (c0 + c2) / 2.0f, xcf = (c1 + c3) / 2.0f; cy = (int)((pad_y + ycf) / s), cx = (int)((pad_x + xcf) / s);
+ *   off4 = ((float)((double)cy + 0.5) - (pad_y + c0)/s, ((pad_y + c2)/s - (float)cy) - 0.5f,
+ *           (float)((double)cx + 0.5) - (pad_x + c1)/s, ((pad_x + c3)/s - (float)cx) - 0.5f).
+ *   A box whose (cy, cx) lies outside the map, or whose label lies outside [0, C), is skipped entirely.
+ *   Radius, float64 (mmdet's gaussian_radius, the corrected roots), m = min_overlap,
+ *     h = ceilf((c2 - c0)/s), w = ceilf((c3 - c1)/s) widened:
+ *     b1 = h + w, k1 = w h (1 - m)/(1 + m), r1 = (b1 - sqrt(b1 b1 - 4 k1)) / 2;
+ *     b2 = 2 (h + w), k2 = (1 - m) w h, r2 = (b2 - sqrt(b2 b2 - 16 k2)) / 8;
+ *     a3 = 4 m, b3 = -2 m (h + w), k3 = (m - 1) w h, r3 = (b3 + sqrt(b3 b3 - 4 a3 k3)) / (2 a3);
+ *     r = max(0, (int)min(r1, r2, r3)).
+ *   Heat, fp32: sigma = (float)(2r + 1) / 6.0f, two_s2 = 2.0f * sigma * sigma; for integer offsets
+ *     |dy| <= r, |dx| <= r from (cy, cx): g = expf(-(float)(dy dy + dx dx) / two_s2) (1.0f at the centre).
+ *   targets[cell][4+c] = max of g over the image's kept boxes of label c, 0 where no disc reaches.
+ *   targets[cell][0..3] = off4 of the last kept box centred on the cell in the stable ascending order of
+ *     the areas (h H)(w W) (the reference's rule: the largest box wins), 0 on every other cell.
+ * cvl_centernet_gauss_norm: targets [B][P][4+C] -> npos[b] (int32) = number of (cell, class) entries of
+ *   image b equal to 1.0f (two same-class boxes on one centre cell count once).  Any target map.
+ * cvl_centernet_gauss_loss: pred [B*P][ld_pred >= 4+C] fp32 (box 0..3, class logits 4..4+C), targets
+ *   [B*P][4+C], N = max(npos[b], 1).  Per class entry with y = its target, e = expf(-|x|),
+ *   L = log1pf(e), p = sigmoid(x) and q = 1 - p formed from e without cancellation,
+ *   -log p = L - min(x, 0), -log q = L + max(x, 0):
+ *     y == 1.0f:  q^alpha (-log p);   otherwise:  (1 - y)^beta p^alpha (-log q)
+ *     (an exponent of 2 or 4 is evaluated as products, any other through powf);
+ *   per box channel j of a cell with some class target == 1.0f: |t_j - x_j|, gradient sign(x_j - t_j), 0
+ *   at equality, applied by selection: the box predictions of every other cell are not used at all.
+ *   losses [B][2] = (cls, reg) = the image's two sums / N, not scaled by the lambdas (the paper's values
+ *   are alpha 2, beta 4); d_pred bf16 [B*P][ld_d >= 4+C] = d(cls_scale*cls + reg_scale*reg)/d(pred),
+ *   channels >= 4+C zeroed.  An image without positives: its negative class sum with N = 1, no box term.
+ *   Sums are float64 per-tile partials and a fixed-order second pass.
+ *   workspace >= cvl_centernet_gauss_loss_workspace_size(B, P) bytes, 8-byte aligned.
+ * Arguments out of range return the invalid-argument status and write nothing.  All three are
+ * graph-safe (no host synchronisation, no allocation, no floating-point atomics) and bit-identical
+ * from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int cvl_centernet_gauss_assign(const float* boxes, const int32_t* nbox, const float* img_dim, int B, int n_max,
+                               int pad_h, int pad_w, int num_classes, int stride, float min_overlap,
+                               float* targets, cvl_stream_t stream);
+int cvl_centernet_gauss_norm(const float* targets, int B, int P, int num_classes, int32_t* npos,
+                             cvl_stream_t stream);
+size_t cvl_centernet_gauss_loss_workspace_size(int B, int P);
+int cvl_centernet_gauss_loss(const float* pred, int ld_pred, const float* targets, const int32_t* npos, int B,
+                             int P, int num_classes, float alpha, float beta, float cls_scale, float reg_scale,
+                             float* losses, void* d_pred, int ld_d, void* workspace, cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Segmented implicit-GEMM convolution (bf16 MFMA, fp32 accumulate).  Replaces every Conv2D of
  * the reference graphs (Keras ResNet50 backbone; FCOS/fcos.py:49-101 FPN, towers and heads;
  * RetinaNet/retinanet_module.py:74-148) forward (mode FWD) and backward-input (mode DGRAD).
