@@ -234,6 +234,8 @@ SIGNATURES = {
     "cvl_resize_pad_normalize": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "cvl_image_augment_workspace_size": (c_size_t, [c_int, c_int]),
     "cvl_image_augment": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    # batched training augmentation (csrc/augment.hip; cvlite/augment.py)
+    "cvl_augment_batch": (c_int, [P, P, c_int, P]),
     "cvl_fcos_detect_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cvl_fcos_detect": (c_int, [P, c_int, P, c_int, c_int, P, P, c_int, c_int, c_float, c_float, c_int, c_int, P, P,
                                 P, P, P, c_size_t, P]),
@@ -285,7 +287,8 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_fcos_gfl_norm_workspace_size", "cvl_fcos_gfl_norm", "cvl_fcos_gfl_loss_workspace_size",
          "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode", "cvl_retina_atss_workspace_size", "cvl_retina_atss_assign",
          "cvl_retina_atss_loss_workspace_size", "cvl_retina_atss_loss", "cvl_centernet_gauss_assign",
-         "cvl_centernet_gauss_norm", "cvl_centernet_gauss_loss_workspace_size", "cvl_centernet_gauss_loss"}
+         "cvl_centernet_gauss_norm", "cvl_centernet_gauss_loss_workspace_size", "cvl_centernet_gauss_loss",
+         "cvl_augment_batch"}
 
 
 def load():

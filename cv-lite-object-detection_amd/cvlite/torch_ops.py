@@ -40,6 +40,10 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           extension): Gaussian heat maps [B, H/s, W/s, 4+C] with
                                                           their object counts [B], and [B, 2] = (cls, reg) per
                                                           image / its objects, with autograd on pred
+  torch.ops.cvlite.augment_images(images, table, ph, pw)  batched training augmentation (cvlite extension;
+                                                          cvlite/augment.py): B decoded images of any sizes
+                                                          and their host descriptor table -> [B, ph, pw, 3]
+                                                          fp32 in one launch
   torch.ops.cvlite.retina_assign(...) / centernet_splat(...)  RetinaNet / CenterNet targets
   torch.ops.cvlite.sgd_clip_(w, g, v, lr, momentum, inv_bs, clip)  clip_by_global_norm + Keras
                                                           SGD momentum, in place
@@ -542,6 +546,24 @@ def _gauss_loss_backward(ctx, g):
 
 
 centernet_gauss_loss.register_autograd(_gauss_loss_backward, setup_context=_gauss_loss_setup)
+
+
+# ---- batched training augmentation (cvlite extension) -------------------------------------------------
+@torch.library.custom_op("cvlite::augment_images", mutates_args=(), device_types="cuda")
+def augment_images(images: List[torch.Tensor], table: torch.Tensor, ph: int, pw: int) -> torch.Tensor:
+    """images: B device uint8 / fp32 [H_i, W_i, 3]; table: host uint8 [B, 144], the images' cvl_augment_desc
+    from cvlite.augment.plan_table (every plan padded to ph x pw) -> [B, ph, pw, 3] fp32: zoom-out, crop,
+    flip, resize, colour, / 127.5 - 1 and pad of the whole batch in one launch (no gradient)."""
+    from . import augment as ag
+    imgs = [ag._device_image(im) for im in images]
+    out = torch.empty((len(imgs), ph, pw, 3), dtype=torch.float32, device=imgs[0].device)
+    ag.launch_table(ag.pinned_table(table, imgs, list(out.unbind(0))))
+    return out
+
+
+@augment_images.register_fake
+def _(images, table, ph, pw):
+    return images[0].new_empty((len(images), ph, pw, 3), dtype=torch.float32)
 
 
 # ---- optimizer -----------------------------------------------------------------------------------

@@ -328,11 +328,14 @@ class JitterFCOSTrainer(object):
         return None if self.l2 is None else self.l2.out
 
 
-def _raw_batch(train_data, idx, rng, jpeg_decode="host"):
+def _raw_batch(train_data, idx, rng, jpeg_decode="host", augment=None):
     """preprocess_data (data_preprocess.py:98-133) of each chosen raw sample: device images of their
     own padded sizes + boxes / counts / unpadded sizes for the bucketed step.  jpeg_decode="gpu":
     the file-name samples of the batch are decoded first, in one cvlite.jpeg.decode_batch call, and
-    preprocess_data takes the decoded device images (the flip / jitter draws keep their order)."""
+    preprocess_data takes the decoded device images (the flip / jitter draws keep their order).
+    augment: a cvlite.augment.AugmentPolicy -- the decoded batch (host-decoded images uploaded as uint8)
+    then goes through ONE cvlite.augment.augment_batch launch instead of one preprocess_data launch
+    per image; None: the path above, untouched."""
     from .data_preprocess import preprocess_data
     if jpeg_decode not in ("host", "gpu"):
         raise ValueError("jpeg_decode must be 'host' or 'gpu', not %r" % (jpeg_decode,))
@@ -342,6 +345,14 @@ def _raw_batch(train_data, idx, rng, jpeg_decode="host"):
         named = [k for k, s in enumerate(samples) if isinstance(s["image"], str)]
         for k, img in zip(named, jpeg.decode_batch([samples[k]["image"] for k in named])):
             samples[k] = dict(samples[k], image=img)
+    if augment is not None:
+        from . import augment as ag
+        from .data_preprocess import _parse_image
+        images = [_parse_image(s["image"]) if isinstance(s["image"], str) else s["image"] for s in samples]
+        return ag.augment_batch(images, [s["objects"]["bbox"] for s in samples],
+                                [s["objects"]["label"] for s in samples], augment, rng,
+                                jitter=[[s["l_jitter"], s["u_jitter"]] for s in samples],
+                                min_side=[s["min_side"] for s in samples], max_side=[s["max_side"] for s in samples])
     imgs, boxes, dims = [], [], []
     for sample in samples:
         img, bbox, cls, shp = preprocess_data(sample, rng=rng)
@@ -412,7 +423,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
           max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07",
           eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0,
-          gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25):
+          gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25, augment=None):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -454,12 +465,23 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       network built with reg_max: ATSS targets, the same divisor and "Average Objs"; the printed
       "Cls / Reg / Cen" averages are then the (qfl, box, dfl) columns, and the eval_data hook evaluates
       through the distribution decode (evaluate_fcos reads reg_max from the network).
+    * augment (cvlite extension, off by default): a cvlite.augment.AugmentPolicy for raw samples -- each
+      batch's decoded images then take photometric distortion, zoom-out, the IoU-constrained random crop,
+      the flip and the jittered resize + pad in ONE cvlite.augment.augment_batch launch (after the one
+      jpeg.decode_batch call when jpeg_decode="gpu"; host-decoded images are uploaded as uint8).  None:
+      today's per-image preprocess_data.  ValueError for pre-processed samples.
     The reference's thermal "Cooling GPU" sleep runs only with CVL_COOLING=1.  Returns None."""
     from . import checkpoint as ck
     import torch.distributed as tdist
     net = getattr(model, "net", model)
     n_data = len(train_data)
     raw = "objects" in train_data[0]
+    if augment is not None:
+        from .augment import AugmentPolicy
+        if not isinstance(augment, AugmentPolicy):
+            raise ValueError("augment must be a cvlite.augment.AugmentPolicy or None, not %r" % (augment,))
+        if not raw:
+            raise ValueError("augment needs raw samples (image + objects), not pre-processed ones")
     dist_on = tdist.is_available() and tdist.is_initialized()
     if world is None:
         world = tdist.get_world_size() if dist_on else 1
@@ -513,7 +535,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
             idx = t.cpu().numpy()
         idx = idx[rank * batch_size:(rank + 1) * batch_size]
         if raw:
-            imgs, bx, nb, dims = _raw_batch(train_data, idx, rng, jpeg_decode)
+            imgs, bx, nb, dims = _raw_batch(train_data, idx, rng, jpeg_decode, augment)
             per_img = trainer.step(imgs, bx, nb, dims).detach().double()
         else:
             imgs, bx, nb, dims = _batch_from_samples(train_data, idx, n_max)

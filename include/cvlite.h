@@ -1393,6 +1393,43 @@ int cvl_image_augment(const float* img_src, float* img_dst, const float* tgt_src
                       const int32_t* ops, const float* params, int B, int N, int S, int T, void* workspace,
                       size_t workspace_bytes, cvl_stream_t stream);
 
+/* Batched training augmentation (cvlite extension, beyond the reference; cvlite/augment.py): one
+ * descriptor per image.  The image's result is defined as this staged fp32 pipeline:
+ *   1. zoom-out: src [H][W][3] (uint8 when src_u8, else fp32) at integer offset (oy, ox) on a canvas
+ *      ch x cw filled with fill[3] (source units); no zoom-out: ch = H, cw = W, oy = ox = 0;
+ *   2. crop: the integer rectangle (y0, x0, hh, ww) of the canvas;
+ *   3. flip: the crop mirrored left-right when flip == 1;
+ *   4. resize: the bilinear resize of cvl_resize_pad_normalize (the same fp32 arithmetic) of the crop
+ *      to oh x ow;
+ *   5. colour: v' = M v + t per pixel, m row-major [3][3], row c = ((m[c][0] * r + m[c][1] * g) +
+ *      m[c][2] * b) + t[c] in fp32 -- the fill goes through it like any other pixel, nothing is clipped;
+ *   6. / 127.5 - 1, zero padded bottom / right to ph x pw, written to dst [ph][pw][3] fp32 (dst may
+ *      point into a batch slot; 16-byte aligned with pw % 4 == 0 takes the 16-byte store path). */
+typedef struct cvl_augment_desc {
+  const void* src;               /* DEVICE [H][W][3] */
+  float* dst;                    /* DEVICE [ph][pw][3] */
+  int32_t src_u8, H, W;
+  int32_t ch, cw, oy, ox;        /* canvas size, source offset on it */
+  int32_t y0, x0, hh, ww;        /* crop rectangle on the canvas */
+  int32_t flip;
+  int32_t oh, ow, ph, pw;        /* resized size, padded size */
+  float m[9], t[3], fill[3];
+  int32_t reserved;              /* 0 (keeps the size a multiple of 8: 144 bytes) */
+} cvl_augment_desc;
+#define CVL_AUGMENT_MAX_BATCH 4096
+#define CVL_AUGMENT_MAX_SIDE 32768
+
+/* Augments B images in ONE launch.  table: HOST array of B descriptors (read here, for the checks and
+ * the grid); table_dev: the same B descriptors in DEVICE memory, copied there by the caller on `stream`
+ * ahead of this call (a pinned host table and one asynchronous copy).  Images of different source, crop
+ * and padded sizes mix; destinations must not overlap each other or a source.  No atomics: deterministic.
+ * Kernel only, no allocation or synchronisation inside.  CVL_EINVAL: B outside [1,
+ * CVL_AUGMENT_MAX_BATCH], a NULL pointer, src_u8 or flip not 0 / 1, a source or a crop that does not
+ * lie inside its canvas, an empty crop, oh > ph or ow > pw, a canvas or padded side above
+ * CVL_AUGMENT_MAX_SIDE, ph * pw >= 2^31. */
+int cvl_augment_batch(const cvl_augment_desc* table /*host[B]*/, const cvl_augment_desc* table_dev, int B,
+                      cvl_stream_t stream);
+
 /* ==========================================================================================
  * JPEG decode (FCOS/data_preprocess.py:5-9 `_parse_image`, tf.image.decode_jpeg): the file bytes
  * -> [H][W][3] uint8 RGB, bit-identical to libjpeg's default decode (islow IDCT, fancy upsampling),
