@@ -230,6 +230,7 @@ struct WgLaunch {
   int tile;                 // co tile width: S 32 / 64 / 128, L 128 / 256, X 128 / 256
   int rows;                 // reduction rows per step: S 64 / 128, X 32 / 64
   bool pf;                  // X: the next step's fragments are read under this step's MFMAs
+  bool reads;               // X, pf: those reads placed one per MFMA gap (false: all x reads after the first row)
   int tiles, co_tiles;      // output tiles per (group, split) and along co; SN: input-channel tiles
   int chunk, nsplit;        // rows per split (WH: 128-row steps) and splits; SN: chunk rows, chunks of all segments
   int steps;                // WH: 128-row steps of the problem
@@ -261,6 +262,7 @@ static inline cvl_conv_desc wgrad_launch_desc(const cvl_conv_desc* d, const WgLa
 struct WgBatchLaunch {
   int kernel, tile;                 // CVL_CK_WG_H / CVL_CK_WG_X (tile 256 / 128) / CVL_CK_NONE
   int n, idx[kWgXMaxProb];          // the problems, as indices into the call's list
+  bool reads;                       // X: as WgLaunch::reads
   int chunk;                        // rows (WH: steps) per workgroup, common to the group
   int nsplit[kWgXMaxProb];
   size_t slab_off[kWgXMaxProb];     // byte offset of each problem's slabs from ws_off

@@ -150,6 +150,7 @@ bool plan_x(const cvl_conv_desc* d, int ngroups, const ConvArgs& a, WgLaunch* l)
   // trace: the reductions 90 -> 63 / 133 -> 100 us per batch, the kernels +1-3 us; FCOS +0.6 %)
   l->rows = best_T == 128 && sr64 ? 64 : 32;
   l->pf = !cvl_dispatch_flag("wg_no_pf") && (best_T == 256 || l->rows == 64);   // (no 32-row 128-wide PF form)
+  l->reads = cvl_dispatch_int("wgx_reads", 1) != 0;   // 0: the PF loop's first read placement (conv_wgrad_x.hip)
   l->co_tiles = (a.Npad + best_T - 1) / best_T;
   l->tiles = l->co_tiles * ((a.K + best_T - 1) / best_T);
   const int forced = cvl_tune_int("CVL_WGX_SPLITS", 0);
@@ -381,6 +382,7 @@ int wgrad_batch_plan(const cvl_conv_desc* const* d, int n, WgradBatchPlan* p) {
     };
     b.kernel = c == 3 ? CVL_CK_WG_H : CVL_CK_WG_X;
     b.tile = c == 3 ? H_BC : c;
+    b.reads = cvl_dispatch_int("wgx_reads", 1) != 0;
     for (int i = 0; i < n; ++i) {
       if (cls[i] != c) continue;
       b.idx[b.n++] = i;

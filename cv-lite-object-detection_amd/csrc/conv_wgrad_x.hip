@@ -52,6 +52,20 @@ constexpr int kMaxGroups = kWgXMaxGroups;
 #define CVL_WGX_ABL 0                     // measurement variants only (ablation bits, see issue())
 #endif
 constexpr unsigned kOOB = 0x80000000u;
+// Where the PF loop issues step t+1's fragment reads inside step t's MFMA segment (template RD):
+//   0  the first form: all x (B) reads in the gap after the first row, a row's two dY (A) reads
+//      after its last MFMA (CVL_DISPATCH=wgx_reads=0)
+//   1  the x reads spread: one (lo, hi) pair per row gap, next to that row's dY reads
+//   2  one read per MFMA gap (two at one gap per row of the 128-wide tile): a row's dY lo read after
+//      its last MFMA, its hi read after the next row's first, one x read per row in between
+//   3  as 2, and a (lo, hi) pair shares one address register (rows rlo and rlo + 4 swizzle alike,
+//      so hi = lo + 4 rows as the instruction's offset field; the second 32-row sub-step likewise),
+//      and the load segment's cursor arithmetic is fenced off the MFMA segment
+// -DCVL_WGX_READS=<n> picks the form the library runs by default (measurement: one library per form).
+#ifndef CVL_WGX_READS
+#define CVL_WGX_READS 3
+#endif
+constexpr int kWgxReads = CVL_WGX_READS;
 
 struct WxArgs {
   ConvArgs a;
@@ -110,13 +124,30 @@ __device__ __forceinline__ unsigned long long memtime_nowait() {
   return t;
 }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// ds_tr16 (conv_common.h) with the instruction's 16-bit byte offset: one address register serves
+// every read a constant apart
+template <int OFF>
+__device__ __forceinline__ s16x4 ds_tr16o(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds offset field");
+  s16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+// rows (+ 4 if hi) of sub-step h (0 or 1) from the address of row rlo of sub-step 0
+template <int HS, int HI>
+__device__ __forceinline__ s16x4 ds_tr16_at(unsigned addr, int h, int hi) {
+  if (h == 0) return hi ? ds_tr16o<HI>(addr) : ds_tr16o<0>(addr);
+  return hi ? ds_tr16o<HS + HI>(addr) : ds_tr16o<HS>(addr);
+}
 
 // PF (round 5): the fragments of step t+1 are read from LDS inside step t's MFMA segment (into a
 // second register set), so a wave's load segment is its DMA issues alone; every wave waits for its
 // pieces of step t+1 at the END of its MFMA segment t-1, so with the groups one barrier apart all
 // pieces of t+1 have landed before the barrier that opens either group's MFMA segment t (the
-// X32 kernel's SW form, conv_igemm_x.hip).
-template <int T, int SR = BR, bool ST = false, bool PF = false, typename Args = WxArgs>
+// X32 kernel's SW form, conv_igemm_x.hip).  RD: where those reads sit between the MFMAs (kWgxReads
+// above; 0 is the first placement).  Every form runs the same MFMAs on the same operands in the
+// same order, so all write the same bits.
+template <int T, int SR = BR, bool ST = false, bool PF = false, typename Args = WxArgs, int RD = 0>
 __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
   constexpr bool MP = !std::is_same<Args, WxArgs>::value;   // a batch of problems (WxBatchArgs)
   using C = WxCfg<T, SR>;
@@ -418,20 +449,35 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
     // one set of dY (A) fragments, re-read row by row right after a row's last MFMA; two sets of
     // x (B) fragments (every row uses all of them)
     s16x4 al[KS][TM], ah[KS][TM], bl[2][KS][TN], bh[2][KS][TN];
-    auto rd_a = [&](unsigned base, int h, int i) {
+    static_assert(KS <= 2 && BCO == BKK, "ds_tr16_at: two sub-steps, one row pitch for both images");
+    constexpr int HI = 4 * BCO * 2, HS = BR * BCO * 2;      // bytes: rows rlo -> rhi, sub-step 0 -> 1
+    // one dY read: row i of sub-step h, rows rlo (hi 0) or rhi (hi 1)
+    auto rd_a1 = [&](unsigned base, int h, int i, int hi) {
       if (abl & 1) return;
-      const unsigned yo = base + h * BR * BCO * 2;
-      al[h][i] = ds_tr16(yo + ya[i]);
-      ah[h][i] = ds_tr16(yo + yb[i]);
+      s16x4 v;
+      if constexpr (RD == 3) v = ds_tr16_at<HS, HI>(base + ya[i], h, hi);
+      else v = ds_tr16(base + h * HS + (hi ? yb[i] : ya[i]));
+      if (hi) ah[h][i] = v;
+      else al[h][i] = v;
+    };
+    auto rd_a = [&](unsigned base, int h, int i) {
+      rd_a1(base, h, i, 0);
+      rd_a1(base, h, i, 1);
+    };
+    // one x read into set b: column block j of sub-step h
+    auto rd_b1 = [&](unsigned base, int b, int h, int j, int hi) {
+      if (abl & 1) return;
+      s16x4 v;
+      if constexpr (RD == 3) v = ds_tr16_at<HS, HI>(base + xa[j], h, hi);
+      else v = ds_tr16(base + h * HS + (hi ? xb[j] : xa[j]));
+      if (hi) bh[b][h][j] = v;
+      else bl[b][h][j] = v;
     };
     auto rd_b = [&](unsigned base, int b) {
-      if (abl & 1) return;
 #pragma unroll
-      for (int h = 0; h < KS; ++h) {
-        const unsigned xo = base + h * BR * BKK * 2;
+      for (int h = 0; h < KS; ++h)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) { bl[b][h][j] = ds_tr16(xo + xa[j]); bh[b][h][j] = ds_tr16(xo + xb[j]); }
-      }
+        for (int j = 0; j < TN; ++j) { rd_b1(base, b, h, j, 0); rd_b1(base, b, h, j, 1); }
     };
 #pragma unroll
     for (int h = 0; h < KS; ++h)
@@ -442,8 +488,13 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
     if (stamp) stamp[1] = wall_clock64();
     if (wco == 1) bar();                        // stagger: waves 4-7 run one barrier behind
     int rslot = 0;
+    constexpr int NRW = KS * TM;                // rows of a segment, in MFMA order
+    static_assert(2 * KS * TN <= NRW, "one x read per row covers the set");
     auto pstep = [&](int b) {
       issue();                                  // step t+3 (out-of-range pieces past the end)
+      const int ns = rslot == NSLOT - 1 ? 0 : rslot + 1;
+      const unsigned nbase = lds0 + ns * (SLOT * 2);
+      if constexpr (RD == 3) __builtin_amdgcn_sched_barrier(0);   // the cursor's advance stays on this side
       bar();
       lgkm_wait();                              // step t's fragments (read in the previous MFMA segment)
 #pragma unroll
@@ -455,8 +506,6 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
       }
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
-      const int ns = rslot == NSLOT - 1 ? 0 : rslot + 1;
-      const unsigned nbase = lds0 + ns * (SLOT * 2);
 #pragma unroll
       for (int h = 0; h < KS; ++h) {
         s16x8 fb[TN];
@@ -465,15 +514,43 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const s16x8 fa = tr_join(al[h][i], ah[h][i]);
+          const int R = h * TM + i;
+          if constexpr (RD >= 2) {
+            // Every MFMA fenced with the reads that follow it.  A dY register is re-read only after
+            // its row's last MFMA (lo at once, hi one MFMA later); the x reads go to the other set.
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            if (abl & 16) acc[i][j][0] += (float)(fa[0] + fb[j][0]);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa),
-                                                                 __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (h == 0 && i == 0) rd_b(nbase, b ^ 1);   // step t+1's x fragments, under the MFMAs
-          rd_a(nbase, h, i);                          // step t+1's dY fragments of this row
-          __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < TN; ++j) {
+              if (abl & 16) acc[i][j][0] += (float)(fa[0] + fb[j][0]);
+              else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa),
+                                                                   __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+              if (j == 0 && R > 0) rd_a1(nbase, (R - 1) / TM, (R - 1) % TM, 1);
+              if (j == (TN > 2 ? 1 : 0) && R < 2 * KS * TN) rd_b1(nbase, b ^ 1, R / (2 * TN), (R / 2) % TN, R & 1);
+              if (j == TN - 1) rd_a1(nbase, h, i, 0);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            if (R == NRW - 1) {
+              rd_a1(nbase, h, i, 1);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              if (abl & 16) acc[i][j][0] += (float)(fa[0] + fb[j][0]);
+              else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa),
+                                                                   __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (RD == 1) {
+              if (R < KS * TN) {                        // step t+1's x fragments: one pair per row gap
+                rd_b1(nbase, b ^ 1, R / TN, R % TN, 0);
+                rd_b1(nbase, b ^ 1, R / TN, R % TN, 1);
+              }
+            } else {
+              if (h == 0 && i == 0) rd_b(nbase, b ^ 1);   // step t+1's x fragments, under the MFMAs
+            }
+            rd_a(nbase, h, i);                          // step t+1's dY fragments of this row
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
       }
       __builtin_amdgcn_s_setprio(0);
@@ -540,6 +617,13 @@ __global__ void __launch_bounds__(NT) conv_wgrad_x_kernel(Args g) {
     __syncthreads();
     if (stamp) stamp[3] = wall_clock64();
   }
+}
+
+// the PF kernel with the library's read placement, or (reads false) the first form
+template <int T, int SR, typename Args>
+void launch_pf(bool reads, dim3 grid, hipStream_t s, const Args& g) {
+  if (reads) hipLaunchKernelGGL((conv_wgrad_x_kernel<T, SR, false, true, Args, kWgxReads>), grid, dim3(NT), 0, s, g);
+  else hipLaunchKernelGGL((conv_wgrad_x_kernel<T, SR, false, true, Args, 0>), grid, dim3(NT), 0, s, g);
 }
 
 #ifdef CVL_MEASURE
@@ -616,13 +700,11 @@ int launch_wg_x(const WgLaunch& l, const cvl_conv_desc& d, const void* x, const 
   } else
 #endif
   if (l.tile == 256) {
-    with_bool(l.pf, [&](auto PF) {
-      hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, decltype(PF)::value>), grid, dim3(NT), 0, s, g);
-    });
+    if (l.pf) launch_pf<256, BR>(l.reads, grid, s, g);
+    else hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR>), grid, dim3(NT), 0, s, g);
   } else if (l.rows == 64) {
-    with_bool(l.pf, [&](auto PF) {
-      hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, decltype(PF)::value>), grid, dim3(NT), 0, s, g);
-    });
+    if (l.pf) launch_pf<128, 64>(l.reads, grid, s, g);
+    else hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64>), grid, dim3(NT), 0, s, g);
   } else {
     hipLaunchKernelGGL((conv_wgrad_x_kernel<128, BR>), grid, dim3(NT), 0, s, g);
   }
@@ -679,10 +761,8 @@ int launch_wg_x_batch(const WgBatchLaunch& b, const cvl_conv_desc* const* d, con
     P.beta = beta;
   }
   for (int i = b.n; i < kMaxProb; ++i) g.p[i].wg0 = 0x7fffffff;
-  if (T == 256)
-    hipLaunchKernelGGL((conv_wgrad_x_kernel<256, BR, false, true, WxBatchArgs>), dim3(wg), dim3(NT), 0, s, g);
-  else
-    hipLaunchKernelGGL((conv_wgrad_x_kernel<128, 64, false, true, WxBatchArgs>), dim3(wg), dim3(NT), 0, s, g);
+  if (T == 256) launch_pf<256, BR>(b.reads, dim3(wg), s, g);
+  else launch_pf<128, 64>(b.reads, dim3(wg), s, g);
   int st = cvl_launch_status();
   for (int i = 0; !st && i < b.n; ++i) {
     const WxProb& P = g.p[i];
