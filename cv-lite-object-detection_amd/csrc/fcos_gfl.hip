@@ -12,6 +12,7 @@
 // written once; only the positive cells (a few per cent) read their 4(R+1) box logits, every other
 // cell writes a zero box-gradient row.  The norm is one more read of the targets and class logits.
 #include "cvl_common.h"
+#include "fcos_focal.h"
 
 #include <math.h>
 
@@ -128,26 +129,6 @@ __device__ __forceinline__ Giou giou_terms(const float (&tt)[4], const float (&d
     o.dG[j] = dGdI * dI + dGdU * (op - dI) + dGdE * dE;
   }
   return o;
-}
-
-// Quality Focal Loss term |y - s|^beta BCE(x, y) and d/dx with y constant (beta = 2 as a product):
-//   d/dx = beta |y - s|^(beta-1) sign(s - y) s (1 - s) BCE + |y - s|^beta (s - y)
-__device__ __forceinline__ float qfl_term(float y, float x, float beta, float* g) {
-  const float e = expf(-fabsf(x));
-  const float s = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);     // sigmoid(x)
-  const float q1 = x >= 0.f ? e / (1.0f + e) : 1.0f / (1.0f + e);    // 1 - sigmoid(x)
-  const float bce = (fmaxf(x, 0.f) - x * y) + log1pf(e);
-  const float df = s - y, a = fabsf(df);
-  float mod, dmod;
-  if (beta == 2.0f) {
-    mod = a * a;
-    dmod = 2.0f * df;
-  } else {
-    mod = powf(a, beta);
-    dmod = a > 0.f ? beta * powf(a, beta - 1.0f) * (df > 0.f ? 1.0f : -1.0f) : 0.f;
-  }
-  *g = dmod * (s * q1) * bce + mod * df;
-  return mod * bce;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -62,6 +62,12 @@ SIGNATURES = {
     "cvl_fcos_gfl_loss": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
                                   c_float, P, P, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
     "cvl_fcos_gfl_decode": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
+    # task-aligned assignment and its loss (csrc/fcos_tal.hip)
+    "cvl_fcos_tal_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "cvl_fcos_tal_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int,
+                                    c_float, c_float, P, P, P, P, P, P, P, c_size_t, P]),
+    "cvl_fcos_tal_loss": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, P,
+                                  P, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
     # CenterNet Gaussian targets and penalty-reduced focal loss (csrc/centernet_gauss.hip)
     "cvl_centernet_gauss_assign": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
     "cvl_centernet_gauss_norm": (c_int, [P, c_int, c_int, c_int, P, P]),
@@ -288,7 +294,7 @@ NEWER = {"cvl_conv_igemm_last_ktile", "cvl_conv_igemm_plan", "cvl_conv_igemm_pla
          "cvl_fcos_gfl_loss", "cvl_fcos_gfl_decode", "cvl_retina_atss_workspace_size", "cvl_retina_atss_assign",
          "cvl_retina_atss_loss_workspace_size", "cvl_retina_atss_loss", "cvl_centernet_gauss_assign",
          "cvl_centernet_gauss_norm", "cvl_centernet_gauss_loss_workspace_size", "cvl_centernet_gauss_loss",
-         "cvl_augment_batch"}
+         "cvl_augment_batch", "cvl_fcos_tal_workspace_size", "cvl_fcos_tal_assign", "cvl_fcos_tal_loss"}
 
 
 def load():

@@ -306,6 +306,81 @@ def fcos_gfl_decode(reg_pred, reg_max, out=None):
     return out
 
 
+# ---- task-aligned assignment (cvlite extension; include/cvlite.h states the rule) ------------------
+def fcos_tal_assign(boxes, nbox, img_dim, pad_hw, num_classes, dist, cls_pred, strides=FCOS_STRIDES, topk=13,
+                    alpha=1.0, beta=6.0, clamp=True, out=None, num_targets=None, return_candidates=False):
+    """Batched task-aligned targets (cvl_fcos_tal_assign; TOOD, Feng et al. 2021): per box the topk cells
+    inside it with the largest sigmoid(class logit)^alpha * IoU(predicted box, box)^beta; per cell the
+    selecting box with the largest IoU wins; slot 4 of a won cell is its metric scaled by max IoU / max
+    metric of its box.  It reads the head outputs, so it runs after the forward: dist [B,P,ld>=4] f32 =
+    (top, bottom, left, right) in stride units (clamp: at 0 first, the 5-output head's raw rows;
+    clamp=False: fcos_gfl_decode's rows), cls_pred [B,P,ld>=C] f32 logits.  Boxes, the targets layout and
+    num_targets (positive cells per level) are fcos_atss_assign's; fcos_target_norm / fcos_tal_loss take
+    the result.  return_candidates: also (cand_cells [B,n_max,topk] i32 by rank or -1, cand_metric and
+    cand_iou the same shape f32, box_max [B,n_max,2] f32 = (max metric, max IoU) over the won cells)."""
+    B, nmax = _boxes_args(boxes, nbox, img_dim)
+    _lib.require_cuda(dist, cls_pred)
+    P = sum(h * w for h, w in fcos_level_shapes(pad_hw[0], pad_hw[1], strides))
+    assert dist.dtype == torch.float32 and cls_pred.dtype == torch.float32
+    assert tuple(dist.shape[:2]) == (B, P) and tuple(cls_pred.shape[:2]) == (B, P)
+    dev = boxes.device
+    if out is None:
+        out = torch.empty((B, P, 5 + num_classes), device=dev, dtype=torch.float32)
+    if num_targets is None:
+        num_targets = torch.empty((B, 5), device=dev, dtype=torch.int32)
+    assert tuple(out.shape) == (B, P, 5 + num_classes) and out.dtype == torch.float32 and out.is_contiguous()
+    assert tuple(num_targets.shape) == (B, 5) and num_targets.dtype == torch.int32 and num_targets.is_contiguous()
+    cand = (None, None, None, None)
+    if return_candidates:
+        k = max(int(topk), 0)
+        cand = (torch.empty((B, nmax, k), device=dev, dtype=torch.int32),
+                torch.empty((B, nmax, k), device=dev, dtype=torch.float32),
+                torch.empty((B, nmax, k), device=dev, dtype=torch.float32),
+                torch.empty((B, nmax, 2), device=dev, dtype=torch.float32))
+    ws = torch.empty(int(_lib.load().cvl_fcos_tal_workspace_size(B, P, nmax)), device=dev, dtype=torch.uint8)
+    st = (_lib.ctypes.c_int32 * 5)(*[int(s) for s in strides])
+    _lib.call("cvl_fcos_tal_assign", ptr(boxes), ptr(nbox), ptr(img_dim), B, nmax, int(pad_hw[0]),
+              int(pad_hw[1]), int(num_classes), _lib.ctypes.cast(st, _lib.c_void_p), ptr(dist), int(dist.shape[2]),
+              1 if clamp else 0, ptr(cls_pred), int(cls_pred.shape[2]), int(topk), float(alpha), float(beta),
+              ptr(out), ptr(num_targets), ptr(cand[0]), ptr(cand[1]), ptr(cand[2]), ptr(cand[3]), ptr(ws),
+              ws.numel(), _lib.stream())
+    return (out, num_targets) + cand if return_candidates else (out, num_targets)
+
+
+def fcos_tal_loss(reg_pred, cls_pred, targets, num_classes, norm=None, grad_scale=1.0, with_grad=True,
+                  grad_dtype=torch.float32, d_reg=None, d_cls=None, beta=2.0, box_weight=2.0, losses=None):
+    """Fused loss on task-aligned targets, forward and backward (cvl_fcos_tal_loss): Quality Focal Loss on
+    the class logits with targets[..., 4] as the positives' class target, GIoU on max(pred, 0) weighted by
+    it, both divided by W = max(sum of targets[..., 4] over the positives, 1) with (count, sum) = norm
+    [B,2] as fcos_target_norm returns it (None: W = 1).  reg_pred [B,P,ld_reg>=5] f32 (column 4, the
+    head's centerness output, is not read and gets zero gradient), cls_pred [B,P,ld_cls>=C] f32, targets
+    [B,P,5+C] f32.  Returns (losses [B,3] f32 = (cls, box, 0) per image, d_reg, d_cls)."""
+    _lib.require_cuda(reg_pred, cls_pred, targets)
+    B, P = _gfl_rows(reg_pred, cls_pred, targets, num_classes)
+    dev = targets.device
+    if norm is not None:
+        _lib.require_cuda(norm)
+        assert tuple(norm.shape) == (B, 2) and norm.dtype == torch.float32 and norm.is_contiguous()
+    if losses is None:
+        losses = torch.empty((B, 3), device=dev, dtype=torch.float32)
+    assert losses.shape == (B, 3) and losses.dtype == torch.float32 and losses.is_contiguous()
+    ws = torch.empty(int(_lib.load().cvl_fcos_loss_workspace_size(B, P)), device=dev, dtype=torch.uint8)
+    if with_grad:
+        if d_reg is None:
+            d_reg = torch.empty((B, P, reg_pred.shape[2]), device=dev, dtype=grad_dtype)
+        if d_cls is None:
+            d_cls = torch.empty((B, P, cls_pred.shape[2]), device=dev, dtype=grad_dtype)
+    for d in (d_reg, d_cls):
+        assert d is None or (d.shape[:2] == (B, P) and d.is_contiguous() and d.dtype in (torch.float32, torch.bfloat16))
+    dt = lambda t: 0 if t is None or t.dtype == torch.float32 else 1  # noqa: E731
+    _lib.call("cvl_fcos_tal_loss", ptr(reg_pred), int(reg_pred.shape[2]), ptr(cls_pred), int(cls_pred.shape[2]),
+              ptr(targets), ptr(norm), B, P, int(num_classes), float(grad_scale), float(beta), float(box_weight),
+              ptr(losses), ptr(d_reg), int(d_reg.shape[2]) if d_reg is not None else 0, dt(d_reg),
+              ptr(d_cls), int(d_cls.shape[2]) if d_cls is not None else 0, dt(d_cls), ptr(ws), ws.numel(),
+              _lib.stream())
+    return losses, d_reg, d_cls
+
+
 def _boxes_args(boxes, nbox, img_dim):
     _lib.require_cuda(boxes, nbox, img_dim)
     assert boxes.dtype == torch.float32 and nbox.dtype == torch.int32 and img_dim.dtype == torch.float32

@@ -29,6 +29,11 @@ gradients through them (the reference's `tf.GradientTape` usage, FCOS/train_fcos
                                                           head (cvlite extension): [B, 3] = (qfl, box,
                                                           dfl) with autograd as fcos_loss, and the
                                                           expected distances for inference
+  torch.ops.cvlite.fcos_tal_assign(boxes, nbox, img_dim, pad_h, pad_w, C, dist, cls, topk, alpha, beta, clamp),
+  torch.ops.cvlite.fcos_tal_loss(reg, cls, targets, norm, C, beta, box_weight)
+                                                          task-aligned assignment from the head outputs
+                                                          (cvlite extension) and its loss: [B, 3] = (cls,
+                                                          box, 0) with autograd as fcos_loss
   torch.ops.cvlite.retina_atss_assign(boxes, nbox, img_dim, pad, anchor_dims, C, topk),
   torch.ops.cvlite.retina_atss_loss(reg, cls, targets, num_targets, img_weight, A, C)
                                                           ATSS for RetinaNet (cvlite extension): compact
@@ -482,6 +487,66 @@ def fcos_gfl_decode(reg: torch.Tensor, reg_max: int) -> torch.Tensor:
 @fcos_gfl_decode.register_fake
 def _(reg, reg_max):
     return reg.new_empty(tuple(reg.shape[:-1]) + (8,))
+
+
+# ---- task-aligned assignment and its loss (cvlite extension) ------------------------------------------
+@torch.library.custom_op("cvlite::fcos_tal_assign", mutates_args=(), device_types="cuda")
+def fcos_tal_assign(boxes: torch.Tensor, nbox: torch.Tensor, img_dim: torch.Tensor, pad_h: int, pad_w: int,
+                    num_classes: int, dist: torch.Tensor, cls: torch.Tensor, topk: int = 13, alpha: float = 1.0,
+                    beta: float = 6.0, clamp: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Task-aligned targets from the head outputs (dist [B,P,>=4] fp32 distances in stride units, clamped
+    at 0 when `clamp`; cls [B,P,>=C] fp32 logits) -> (targets [B,P,5+C] fp32 level-major with the
+    alignment value in slot 4, positive cells per level [B,5] i32); the loss op is fcos_tal_loss.  No
+    gradient flows through it (the targets are constants for the loss)."""
+    return ot.fcos_tal_assign(boxes.contiguous(), nbox.contiguous(), img_dim.contiguous(), (pad_h, pad_w),
+                              num_classes, dist.contiguous(), cls.contiguous(), topk=topk, alpha=alpha, beta=beta,
+                              clamp=clamp)
+
+
+@fcos_tal_assign.register_fake
+def _(boxes, nbox, img_dim, pad_h, pad_w, num_classes, dist, cls, topk=13, alpha=1.0, beta=6.0, clamp=True):
+    P = sum(h * w for h, w in ot.fcos_level_shapes(pad_h, pad_w))
+    B = boxes.shape[0]
+    return boxes.new_empty((B, P, 5 + num_classes)), nbox.new_empty((B, 5))
+
+
+@torch.library.custom_op("cvlite::fcos_tal_loss", mutates_args=(), device_types="cuda")
+def fcos_tal_loss(reg: torch.Tensor, cls: torch.Tensor, targets: torch.Tensor, norm: Optional[torch.Tensor],
+                  num_classes: int, beta: float = 2.0, box_weight: float = 2.0) -> torch.Tensor:
+    """Loss on task-aligned targets per image: reg [B,P,>=5] fp32, cls [B,P,>=C] fp32, targets [B,P,5+C],
+    norm [B,2] from fcos_target_norm (None: plain sums) -> [B,3] = (cls, box, 0)."""
+    losses, _, _ = ot.fcos_tal_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), num_classes,
+                                    norm=None if norm is None else norm.contiguous(), with_grad=False, beta=beta,
+                                    box_weight=box_weight)
+    return losses
+
+
+@fcos_tal_loss.register_fake
+def _(reg, cls, targets, norm, num_classes, beta=2.0, box_weight=2.0):
+    return reg.new_empty((reg.shape[0], 3))
+
+
+def _tal_loss_setup(ctx, inputs, output):
+    reg, cls, targets, norm, C, beta, wb = inputs
+    ctx.save_for_backward(reg, cls, targets, norm)
+    ctx.args = (C, beta, wb)
+
+
+def _tal_loss_backward(ctx, g):
+    reg, cls, targets, norm = ctx.saved_tensors
+    C, beta, wb = ctx.args
+    _, d_reg, d_cls = ot.fcos_tal_loss(reg.contiguous(), cls.contiguous(), targets.contiguous(), C,
+                                       norm=None if norm is None else norm.contiguous(), grad_scale=1.0, beta=beta,
+                                       box_weight=wb)
+    g = g.to(torch.float32)
+    # cls term -> class logits, box term -> the box outputs (columns 4.. are zero already); the padding
+    # columns get exactly zero
+    cscale = torch.zeros((reg.shape[0], 1, cls.shape[2]), dtype=torch.float32, device=reg.device)
+    cscale[:, 0, :C] = g[:, 0:1]
+    return d_reg * g[:, 1].view(-1, 1, 1), d_cls * cscale, None, None, None, None, None
+
+
+fcos_tal_loss.register_autograd(_tal_loss_backward, setup_context=_tal_loss_setup)
 
 
 # ---- CenterNet Gaussian targets and penalty-reduced focal loss (cvlite extension) ---------------------

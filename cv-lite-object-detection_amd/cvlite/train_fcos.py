@@ -35,16 +35,16 @@ class SGD(object):
         self.momentum = float(momentum)
 
 
-TARGET_KINDS = ("fcos", "center", "center_v1", "paper", "atss", "gfl")
+TARGET_KINDS = ("fcos", "center", "center_v1", "paper", "atss", "gfl", "tal")
 
 
 def check_recipe(net, targets):
     """The network / targets pairs the trainers take (ValueError otherwise, before any device work):
-    "paper", "atss" and "gfl" need the FCOS network, "gfl" one built with reg_max, and a network built
-    with reg_max trains with "gfl" only (every other loss reads a 5-output box head)."""
+    "paper", "atss", "gfl" and "tal" need the FCOS network, "gfl" one built with reg_max, and a network
+    built with reg_max trains with "gfl" only (every other loss reads a 5-output box head)."""
     if targets not in TARGET_KINDS:
-        raise ValueError("targets must be 'fcos', 'center', 'center_v1', 'paper', 'atss' or 'gfl'")
-    if targets in ("paper", "atss", "gfl") and hasattr(net, "cen_heads"):
+        raise ValueError("targets must be 'fcos', 'center', 'center_v1', 'paper', 'atss', 'gfl' or 'tal'")
+    if targets in ("paper", "atss", "gfl", "tal") and hasattr(net, "cen_heads"):
         raise ValueError("targets=%r needs the FCOS network, not a centre variant" % (targets,))
     reg_max = getattr(net, "reg_max", None)
     if targets == "gfl" and reg_max is None:
@@ -58,7 +58,8 @@ class FCOSTrainer(GraphStepper):
                  decay_rate=0.9, momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0,
                  world=1, use_graph=True, st_step=0, targets="fcos", center_only=True, optimizer=None,
                  max_decays=None, center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0, gfl_beta=2.0,
-                 gfl_box_weight=2.0, gfl_dfl_weight=0.25):
+                 gfl_box_weight=2.0, gfl_dfl_weight=0.25, tal_topk=13, tal_alpha=1.0, tal_beta=6.0,
+                 tal_box_weight=2.0, tal_warmup=0):
         self.net = net
         # optimizer: None or SGD -> Keras SGD with `momentum` (train_fcos.py:284-285); an Adam
         # (cvlite.train_centernet.Adam, the tf.optimizers.Adam() stand-in) -> Keras Adam, what the
@@ -95,10 +96,29 @@ class FCOSTrainer(GraphStepper):
         # the forward, fcos_gfl_norm (it reads the class outputs, so it follows the forward) and
         # fcos_gfl_loss (QFL with exponent gfl_beta, GIoU weighted gfl_box_weight, DFL weighted
         # gfl_dfl_weight; per-image normalisation); losses columns are then (qfl, box, dfl)
+        # "tal" (cvlite extension): task-aligned assignment (TOOD) on the plain FCOS network -- the forward,
+        # then fcos_tal_assign on the head outputs (the tal_topk inside cells per box with the largest
+        # score^tal_alpha * IoU^tal_beta), fcos_target_norm and fcos_tal_loss (QFL against the alignment
+        # target, GIoU weighted tal_box_weight; the centerness output gets no gradient); losses columns
+        # are then (cls, box, 0).  The first tal_warmup steps assign with fcos_atss_assign (atss_topk,
+        # atss_scale) under the same norm and loss -- at initialisation the predicted boxes overlap
+        # nothing, so the metric says nothing -- and the step after them re-captures the graphs once.
         check_recipe(net, targets)
         self.target_kind, self.center_only = targets, center_only
         self.atss_topk, self.atss_scale = int(atss_topk), float(atss_scale)
         self.gfl = (float(gfl_beta), float(gfl_box_weight), float(gfl_dfl_weight))
+        self.tal = (int(tal_topk), float(tal_alpha), float(tal_beta), float(tal_box_weight))
+        if targets == "tal":
+            if not 1 <= self.tal[0] <= 32:
+                raise ValueError("tal_topk must be in 1..32, not %r" % (tal_topk,))
+            if not (self.tal[1] >= 0.0 and self.tal[2] >= 0.0):
+                raise ValueError("tal_alpha and tal_beta must be >= 0, not %r, %r" % (tal_alpha, tal_beta))
+            if int(tal_warmup) < 0:
+                raise ValueError("tal_warmup must be >= 0, not %r" % (tal_warmup,))
+        # tal_warm: this step assigns with ATSS.  A trainer with tal_warmup > 0 leaves the warm-up by its own
+        # step count; JitterFCOSTrainer builds its buckets with tal_warmup 0 and sets their tal_warm itself.
+        self.tal_warmup, self.tal_steps = int(tal_warmup), 0
+        self.tal_warm = targets == "tal" and self.tal_warmup > 0
         self.center_radius = float(center_radius)
         self.bounds = tuple(float(v) for v in (ot.FCOS_PAPER_BOUNDS if bounds is None else bounds))
         # the centre networks (cvlite.fcos_center_net): focal centerness from the cls-tower head in
@@ -123,8 +143,8 @@ class FCOSTrainer(GraphStepper):
                                  dtype=act, device=dev)
         self.d_cls = torch.zeros((B, self.P, net.cls_ld), dtype=act, device=dev)
         self.losses = torch.zeros((B, 3), dtype=torch.float32, device=dev)
-        self.norm = (torch.zeros((B, 2), dtype=torch.float32, device=dev) if targets in ("paper", "atss", "gfl")
-                     else None)
+        self.norm = (torch.zeros((B, 2), dtype=torch.float32, device=dev)
+                     if targets in ("paper", "atss", "gfl", "tal") else None)
         # the heads' fp32 outputs, zeroed once (FCOSNet writes only the used columns; see
         # FCOSNet._heads_forward) -- lent to the network for the step's forward only
         self._head_out = ((torch.zeros((B, self.P, net.reg_ld), dtype=torch.float32, device=dev),
@@ -157,6 +177,11 @@ class FCOSTrainer(GraphStepper):
             tg, _ = ot.fcos_atss_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
                                         topk=self.atss_topk, anchor_scale=self.atss_scale, out=self.targets,
                                         num_targets=self.ntgt)
+        elif self.target_kind == "tal":           # the assignment reads the head outputs: after the forward,
+            tg = self.targets                     # except in the warm-up, which assigns with ATSS
+            if self.tal_warm:
+                ot.fcos_atss_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
+                                    topk=self.atss_topk, anchor_scale=self.atss_scale, out=tg, num_targets=self.ntgt)
         elif self.target_kind == "center":
             tg, _ = ot.fcos_center_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C,
                                           center_only=self.center_only, out=self.targets, num_targets=self.ntgt)
@@ -177,6 +202,14 @@ class FCOSTrainer(GraphStepper):
             ot.fcos_gfl_norm(cls, tg, self.C, out=self.norm)
             ot.fcos_gfl_loss(reg, cls, tg, self.C, self.net.reg_max, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
                              d_cls=self.d_cls, beta=beta, box_weight=w_box, dfl_weight=w_dfl, losses=self.losses)
+        elif self.target_kind == "tal":
+            topk, alpha, beta, w_box = self.tal
+            if not self.tal_warm:
+                ot.fcos_tal_assign(self.boxes, self.nbox, self.img_dim, (self.H, self.W), self.C, reg, cls, topk=topk,
+                                   alpha=alpha, beta=beta, clamp=True, out=tg, num_targets=self.ntgt)
+            ot.fcos_target_norm(tg, self.C, out=self.norm)
+            ot.fcos_tal_loss(reg, cls, tg, self.C, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
+                             d_cls=self.d_cls, box_weight=w_box, losses=self.losses)
         elif self.target_kind in ("paper", "atss"):
             ot.fcos_paper_loss(reg, cls, tg, self.C, norm=self.norm, grad_scale=1.0, d_reg=self.d_reg,
                                d_cls=self.d_cls, losses=self.losses)
@@ -195,6 +228,23 @@ class FCOSTrainer(GraphStepper):
             nn.sgd_clip_update(st.flat, st.grad, st.mom, self.lr, self.momentum, 1.0 / (self.B * self.world),
                                self.clip, ws=self.sumsq)
         self.net.pack()
+
+    # ---- the task-aligned warm-up --------------------------------------------------------------------
+    def _tal_tick(self):
+        """Counts a step; the step after the last warm-up step switches to the task-aligned assignment
+        and drops the captured graphs (one re-capture)."""
+        if self.tal_warm and self.tal_warmup > 0 and self.tal_steps >= self.tal_warmup:
+            self.tal_warm = False
+            self.invalidate()
+        self.tal_steps += 1
+
+    def step(self):
+        self._tal_tick()
+        return GraphStepper.step(self)
+
+    def run_fwd_bwd(self):
+        self._tal_tick()
+        return GraphStepper.run_fwd_bwd(self)
 
     def load_batch(self, images, boxes, nbox, img_dim=None):
         """Device-to-device copy of one batch into the static input buffers.  img_dim [B,2]: the
@@ -230,7 +280,8 @@ class JitterFCOSTrainer(object):
     def __init__(self, net, batch_size, n_max=16, init_lr=5e-4, min_lr=1e-5, decay_step=1000, decay_rate=0.9,
                  momentum=0.9, gradient_clip=1.0, reg_type="l1", weight_decay=0.0, st_step=0, use_graph=True,
                  max_buckets=12, world=1, optimizer=None, max_decays=None, targets="fcos", center_radius=1.5,
-                 bounds=None, atss_topk=9, atss_scale=8.0, gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25):
+                 bounds=None, atss_topk=9, atss_scale=8.0, gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25,
+                 tal_topk=13, tal_alpha=1.0, tal_beta=6.0, tal_box_weight=2.0, tal_warmup=0):
         # world > 1: data-parallel (dist.py) -- each rank runs its own bs images through its buckets,
         # the summed gradient is all-reduced (one bucketed SUM over RCCL) before the shared update
         # with 1 / (world * bs); the buckets differ per rank, so there is no overlap with the backward
@@ -242,11 +293,18 @@ class JitterFCOSTrainer(object):
         self.reg_type, self.use_graph, self.max_buckets = reg_type, use_graph, max_buckets
         # targets / center_radius / bounds / atss_topk / atss_scale / gfl_*: forwarded to every bucket's
         # FCOSTrainer ("paper": the FCOS papers' recipe; "atss": ATSS targets under the same loss; "gfl":
-        # Generalized Focal Loss on ATSS targets, a network built with reg_max)
+        # Generalized Focal Loss on ATSS targets, a network built with reg_max; "tal": task-aligned assignment
+        # and its loss).  The "tal" warm-up is counted here, in steps of this trainer, and all buckets leave
+        # it together: they are built with tal_warmup 0 and take their tal_warm from this trainer.
         check_recipe(net, targets)
         self.bucket_kw = dict(targets=targets, center_radius=center_radius, bounds=bounds, atss_topk=atss_topk,
                               atss_scale=atss_scale, gfl_beta=gfl_beta, gfl_box_weight=gfl_box_weight,
-                              gfl_dfl_weight=gfl_dfl_weight)
+                              gfl_dfl_weight=gfl_dfl_weight, tal_topk=tal_topk, tal_alpha=tal_alpha,
+                              tal_beta=tal_beta, tal_box_weight=tal_box_weight)
+        if targets == "tal" and int(tal_warmup) < 0:
+            raise ValueError("tal_warmup must be >= 0, not %r" % (tal_warmup,))
+        self.tal_warmup, self.tal_steps = int(tal_warmup), 0
+        self.tal_warm = targets == "tal" and self.tal_warmup > 0
         self.weight_decay = float(weight_decay)
         self.l2 = nn.L2Reg(net.store) if self.weight_decay > 0.0 else None
         dev = net.device
@@ -270,6 +328,9 @@ class JitterFCOSTrainer(object):
                 self.buckets.pop(next(iter(self.buckets)))
             tr = FCOSTrainer(self.net, count, (size, size), n_max=self.n_max, reg_type=self.reg_type,
                              use_graph=self.use_graph, **self.bucket_kw)
+        if tr.tal_warm != self.tal_warm:                       # a new bucket, or the warm-up has ended
+            tr.tal_warm = self.tal_warm
+            tr.invalidate()
         self.buckets[key] = tr
         return tr
 
@@ -285,6 +346,9 @@ class JitterFCOSTrainer(object):
         img_dim = torch.as_tensor(img_dim, dtype=torch.float32, device=dev)
         if self.l2 is not None:
             self.l2.run()
+        if self.tal_warm and self.tal_steps >= self.tal_warmup:
+            self.tal_warm = False
+        self.tal_steps += 1
         sizes = [int(t.shape[0]) for t in images]
         first = True
         for S in sorted(set(sizes)):
@@ -423,7 +487,8 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
           step_cool=1000, weight_decay=1.0e-4, gradient_clip=1.0, save_loss_file="train_losses.csv", world=None,
           max_decays=None, jpeg_decode="host", eval_data=None, eval_every=0, eval_protocol="voc07",
           eval_fold_bn=False, recipe="reference", center_radius=1.5, bounds=None, atss_topk=9, atss_scale=8.0,
-          gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25, augment=None):
+          gfl_beta=2.0, gfl_box_weight=2.0, gfl_dfl_weight=0.25, augment=None, tal_topk=13, tal_alpha=1.0,
+          tal_beta=6.0, tal_box_weight=2.0, tal_warmup=0):
     """Same keywords and defaults as FCOS/train_fcos.py:87-93.
     * `model`: what cvlite.fcos.build_model returns (or its FCOSNet).
     * `train_data`: either the reference's raw samples dict(image = a JPEG / PNG file name (decoded
@@ -464,7 +529,12 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
       (FCOSTrainer(targets="gfl", atss_topk, atss_scale, gfl_beta, gfl_box_weight, gfl_dfl_weight)) on a
       network built with reg_max: ATSS targets, the same divisor and "Average Objs"; the printed
       "Cls / Reg / Cen" averages are then the (qfl, box, dfl) columns, and the eval_data hook evaluates
-      through the distribution decode (evaluate_fcos reads reg_max from the network).
+      through the distribution decode (evaluate_fcos reads reg_max from the network).  "tal" = task-aligned
+      assignment (FCOSTrainer(targets="tal", tal_topk, tal_alpha, tal_beta, tal_box_weight, tal_warmup,
+      atss_topk, atss_scale)) on the plain FCOS network: the positives are chosen after the forward from
+      the head outputs, the first tal_warmup steps assign with ATSS; the printed "Cls / Reg / Cen" averages
+      are then the (cls, box, 0) columns, and the eval_data hook evaluates with the box outputs clamped at 0
+      and the class score alone (center=False), as that loss trains them.
     * augment (cvlite extension, off by default): a cvlite.augment.AugmentPolicy for raw samples -- each
       batch's decoded images then take photometric distortion, zoom-out, the IoU-constrained random crop,
       the flip and the jittered resize + pad in ONE cvlite.augment.augment_batch launch (after the one
@@ -493,10 +563,10 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
         raise ValueError("train_data holds %d samples, fewer than world * batch_size" % n_data)
     say = print if rank == 0 else (lambda *a, **k: None)
     momentum = float(getattr(optimizer, "momentum", 0.9))
-    if recipe not in ("reference", "paper", "atss", "gfl"):
-        raise ValueError("recipe must be 'reference', 'paper', 'atss' or 'gfl', not %r" % (recipe,))
-    if recipe == "atss" and hasattr(net, "cen_heads"):
-        raise ValueError("recipe='atss' needs the FCOS network, not a centre variant")
+    if recipe not in ("reference", "paper", "atss", "gfl", "tal"):
+        raise ValueError("recipe must be 'reference', 'paper', 'atss', 'gfl' or 'tal', not %r" % (recipe,))
+    if recipe in ("atss", "tal") and hasattr(net, "cen_heads"):
+        raise ValueError("recipe=%r needs the FCOS network, not a centre variant" % (recipe,))
     if recipe == "gfl" or getattr(net, "reg_max", None) is not None:
         check_recipe(net, "gfl" if recipe == "gfl" else "fcos" if recipe == "reference" else recipe)
     recipe_kw = {}
@@ -507,6 +577,10 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
     elif recipe == "gfl":
         recipe_kw = dict(targets="gfl", atss_topk=atss_topk, atss_scale=atss_scale, gfl_beta=gfl_beta,
                          gfl_box_weight=gfl_box_weight, gfl_dfl_weight=gfl_dfl_weight)
+    elif recipe == "tal":
+        recipe_kw = dict(targets="tal", atss_topk=atss_topk, atss_scale=atss_scale, tal_topk=tal_topk,
+                         tal_alpha=tal_alpha, tal_beta=tal_beta, tal_box_weight=tal_box_weight,
+                         tal_warmup=tal_warmup)
     if raw:          # reference-format samples: per-image jittered sizes, shape-bucketed step
         n_max = max(16, max(len(s["objects"]["label"]) for s in train_data))
         trainer = JitterFCOSTrainer(net, batch_size, n_max=n_max, init_lr=init_lr, min_lr=min_lr,
@@ -597,7 +671,7 @@ def train(train_data, training_loss, model, batch_size, optimizer, ckpt, ck_mana
         if eval_data is not None and eval_every > 0 and (step + 1) % eval_every == 0 and rank == 0:
             from .evaluate import evaluate_fcos
             res = evaluate_fcos(net, eval_data, net.C, batch_size=batch_size, protocol=eval_protocol,
-                                fold_bn=eval_fold_bn, clamp_reg=recipe in ("paper", "atss"))
+                                fold_bn=eval_fold_bn, center=False, clamp_reg=recipe in ("paper", "atss", "tal"))
             say("Eval mAP:", str(res["mAP"]))
         if (step + 1) % step_cool == 0:
             say("Trend Loss:", str(round(trend_loss / step_cool, 5)))

@@ -332,6 +332,81 @@ int cvl_fcos_gfl_decode(const float* reg_pred, int ld_reg, int rows, int reg_max
                         cvl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Task-aligned assignment for the FCOS head (Feng et al., ICCV 2021, "TOOD: Task-aligned One-stage
+ * Object Detection") and its loss: an extension beyond the reference, the step after the geometric
+ * assigners above.  The network's own outputs choose its positives: a cell is positive for a box when
+ * its class score and the IoU of its predicted box are jointly high, and the class target of a positive
+ * is that alignment value instead of a one-hot 1.  The assignment therefore runs AFTER the forward.
+ * Compiled without contraction; fp32 in this operation order unless float64 is named.
+ *
+ * cvl_fcos_tal_assign: boxes, validity, cell positions, the target layout and num_targets exactly as
+ * cvl_fcos_atss_assign (boxes [B][n_max][5] = (yc, xc, h, w, label) normalised, skipped unless
+ * -1 < label < C and area > 0; gy = ((float)cy + 0.5f)*sf; targets [B][P][5+C] level-major; num_targets
+ * [B][5] = POSITIVE CELLS per level; n_max <= 256; the staged tile limits C to 219).
+ * dist [B][P][ld_dist >= 4] = the predicted distances (top, bottom, left, right) in stride units: with
+ * clamp != 0, d_j = fmaxf(v_j, 0) (the 5-output head's raw reg_pred is passed directly); with clamp == 0,
+ * d_j = v_j (the layout cvl_fcos_gfl_decode writes).  cls_pred [B][P][ld_cls >= C] = fp32 class logits.
+ * topk in 1..32 (the papers' 13), alpha >= 0 and beta >= 0 (the papers' 1 and 6); anything outside
+ * these limits returns the invalid-argument status and writes nothing.
+ *   per (box i, cell p):
+ *     inside: t = gy - y0, b = y1 - gy, l = gx - x0, r = x1 - gx, each > 0.01f (rule 4 of ATSS); the
+ *       predictions of a cell are read only for the boxes it lies inside, so cells outside every valid
+ *       box may hold anything, a NaN included
+ *     predicted box: py0 = gy - d0*sf, py1 = gy + d1*sf, px0 = gx - d2*sf, px1 = gx + d3*sf;
+ *       ih = fmaxf(fminf(y1, py1) - fmaxf(y0, py0), 0), iw likewise in x; inter = ih*iw;
+ *       uni = ((py1 - py0)*(px1 - px0) + area) - inter;
+ *       u = uni > 0 ? (float)((double)inter / (double)uni) : 0
+ *     score: s = 1/(1 + expf(-x)), x = cls_pred[b][p][(int)label]
+ *     metric: m = pow_a(s) * pow_b(u); alpha == 1 is evaluated as s, beta == 6 as u2 = u*u, (u2*u2)*u2,
+ *       other exponents through powf
+ *   candidates of box i: the inside cells with m > 0 (a NaN metric is never a candidate); selected: the
+ *     min(topk, #candidates) candidates with the largest m, ties to the lowest global cell index, ranked
+ *     in that order (the inside-first order of PP-YOLOE / YOLOv8)
+ *   per cell: among the boxes that selected it the largest u wins, ties to the lowest box index (a
+ *     64-bit integer max of u bits << 32 | ~box, as the ATSS contest)
+ *   per box: max_m and max_u over the cells it won (integer max of the bit patterns; both are >= 0)
+ *   the row of a won cell: (t, b, l, r)/sf; slot 4 = (float)((double)m * (double)max_u /
+ *     ((double)max_m + 1e-9)); a one-hot class.  All other rows are zero.
+ * Optional outputs (null: not written): cand_cells int32 [B][n_max][topk] = the selected global cell
+ * by rank, or -1; cand_metric and cand_iou fp32 of the same shape, 0 where the cell is -1; box_max float
+ * [B][n_max][2] = (max_m, max_u), 0 for a box that won nothing.  workspace >=
+ * cvl_fcos_tal_workspace_size(B, P, n_max) bytes, 8-byte aligned.  Graph-safe: no host synchronisation,
+ * no allocation; its clears are memset nodes.  Bit-identical from run to run (the contests are integer
+ * maxima, the counts integer adds), whatever path the selection takes: a box's candidate keys are staged
+ * in LDS, and a box with more candidates than the stage holds recomputes them in every round.
+ *
+ * cvl_fcos_tal_loss: fused forward + backward with the conventions, argument order and workspace rule
+ * of cvl_fcos_paper_loss (reg_pred [B][P][ld_reg >= 5], cls_pred [B][P][ld_cls >= C], optional d_reg /
+ * d_cls fp32 (0) or bf16 (1) with padding columns zeroed, grad_scale, losses [B][3], workspace >=
+ * cvl_fcos_loss_workspace_size(B, P) bytes), with qfl_beta >= 0 and w_box (the papers' 2 and 2) in the
+ * place of alpha and gamma.  A cell is positive when max_c targets[5+c] >= 1; y_c = targets[4] where
+ * targets[5+c] >= 1 (such a cell is positive), else 0.  W = max(norm[b][1], 1) with norm [B][2] as
+ * cvl_fcos_target_norm writes it (count, sum of slot 4); a null norm gives W = 1.
+ *   cls = (1/W) sum_cells sum_c |y_c - s_c|^qfl_beta * (max(x,0) - x*y_c + log1p(exp(-|x|))), the QFL term
+ *     of cvl_fcos_gfl_loss with y a constant for the gradient
+ *   box = (w_box/W) sum_pos targets[4] * (1 - GIoU), GIoU exactly the expressions of cvl_fcos_paper_loss
+ *     on d_j = max(p_j, 0)
+ *   losses[b] = (cls, box, 0)
+ * Column 4 and up of d_reg is zero (the head's centerness output gets no gradient); non-positive cells
+ * get all-zero box rows, and their box outputs are not read.  Per-image sums are float64 per-tile
+ * partials and a fixed-order second pass.  The normalisation is per image (the published code
+ * normalises over the batch).  Arguments out of range return the invalid-argument status and write
+ * nothing.  Graph-safe.
+ * ---------------------------------------------------------------------------------------- */
+size_t cvl_fcos_tal_workspace_size(int B, int P, int n_max);
+int cvl_fcos_tal_assign(const float* boxes, const int32_t* nbox, const float* img_dim, int B, int n_max,
+                        int pad_h, int pad_w, int num_classes, const int32_t* strides /*host[5]*/,
+                        const float* dist, int ld_dist, int clamp, const float* cls_pred, int ld_cls, int topk,
+                        float alpha, float beta, float* targets, int32_t* num_targets, int32_t* cand_cells,
+                        float* cand_metric, float* cand_iou, float* box_max, void* workspace,
+                        size_t workspace_bytes, cvl_stream_t stream);
+int cvl_fcos_tal_loss(const float* reg_pred, int ld_reg, const float* cls_pred, int ld_cls,
+                      const float* targets, const float* norm, int B, int P, int num_classes,
+                      float grad_scale, float qfl_beta, float w_box, float* losses, void* d_reg, int ld_dreg,
+                      int dreg_dtype, void* d_cls, int ld_dcls, int dcls_dtype, void* workspace,
+                      size_t workspace_bytes, cvl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * CenterNet as the paper trains it (Zhou et al., 2019, "Objects as Points"): an extension beyond the
  * reference.  Gaussian heat about every object centre, the penalty-reduced focal loss, L1 on the box
  * channels of the centres, every sum divided by the image's number of objects.  The reference's recipe
