@@ -50,6 +50,15 @@ __device__ __forceinline__ s16x4 ds_tr16(unsigned addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
   return v;
 }
+// ds_tr16 with the instruction's 16-bit byte offset: one address register serves every read a
+// lane-uniform constant apart
+template <int OFF>
+__device__ __forceinline__ s16x4 ds_tr16o(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds offset field");
+  s16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
 __device__ __forceinline__ void lgkm_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void tr_pin(s16x4& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ s16x8 tr_join(s16x4 l, s16x4 h) {
@@ -230,7 +239,8 @@ struct WgLaunch {
   int tile;                 // co tile width: S 32 / 64 / 128, L 128 / 256, X 128 / 256
   int rows;                 // reduction rows per step: S 64 / 128, X 32 / 64
   bool pf;                  // X: the next step's fragments are read under this step's MFMAs
-  bool reads;               // X, pf: those reads placed one per MFMA gap (false: all x reads after the first row)
+  bool reads;               // X, pf: those reads placed one per MFMA gap (false: all x reads after the first row);
+                            // WH: the pipelined step loop (false: the first form)
   int tiles, co_tiles;      // output tiles per (group, split) and along co; SN: input-channel tiles
   int chunk, nsplit;        // rows per split (WH: 128-row steps) and splits; SN: chunk rows, chunks of all segments
   int steps;                // WH: 128-row steps of the problem
@@ -262,7 +272,7 @@ static inline cvl_conv_desc wgrad_launch_desc(const cvl_conv_desc* d, const WgLa
 struct WgBatchLaunch {
   int kernel, tile;                 // CVL_CK_WG_H / CVL_CK_WG_X (tile 256 / 128) / CVL_CK_NONE
   int n, idx[kWgXMaxProb];          // the problems, as indices into the call's list
-  bool reads;                       // X: as WgLaunch::reads
+  bool reads;                       // as WgLaunch::reads
   int chunk;                        // rows (WH: steps) per workgroup, common to the group
   int nsplit[kWgXMaxProb];
   size_t slab_off[kWgXMaxProb];     // byte offset of each problem's slabs from ws_off

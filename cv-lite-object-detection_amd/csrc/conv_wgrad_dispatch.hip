@@ -77,6 +77,7 @@ bool plan_h(const cvl_conv_desc* d, int ngroups, WgLaunch* l) {
   l->tile = H_BC;
   l->tiles = (d->Cin / H_BC) * (d->n_store / H_BC);
   l->steps = d->B * d->seg[0].Hr * d->seg[0].Wr / H_RS;
+  l->reads = cvl_dispatch_int("wh_reads", 1) != 0;   // 0: the first form of the step loop (conv_wgrad_h.hip)
   int ns = (cvl_tune_int("CVL_WGH_WGS", 256) + l->tiles - 1) / l->tiles;
   if (ns > l->steps / 4) ns = l->steps / 4;
   if (ns < 1) ns = 1;
@@ -382,7 +383,7 @@ int wgrad_batch_plan(const cvl_conv_desc* const* d, int n, WgradBatchPlan* p) {
     };
     b.kernel = c == 3 ? CVL_CK_WG_H : CVL_CK_WG_X;
     b.tile = c == 3 ? H_BC : c;
-    b.reads = cvl_dispatch_int("wgx_reads", 1) != 0;
+    b.reads = cvl_dispatch_int(c == 3 ? "wh_reads" : "wgx_reads", 1) != 0;
     for (int i = 0; i < n; ++i) {
       if (cls[i] != c) continue;
       b.idx[b.n++] = i;

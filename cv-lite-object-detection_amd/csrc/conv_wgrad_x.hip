@@ -124,15 +124,6 @@ __device__ __forceinline__ unsigned long long memtime_nowait() {
   return t;
 }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// ds_tr16 (conv_common.h) with the instruction's 16-bit byte offset: one address register serves
-// every read a constant apart
-template <int OFF>
-__device__ __forceinline__ s16x4 ds_tr16o(unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds offset field");
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
 // rows (+ 4 if hi) of sub-step h (0 or 1) from the address of row rlo of sub-step 0
 template <int HS, int HI>
 __device__ __forceinline__ s16x4 ds_tr16_at(unsigned addr, int h, int hi) {
